@@ -36,12 +36,15 @@ def _oracle_step_factory(args, rank, world, dev):
     def step():
         rp, rd, tm = o.raydirs(s["campos"][sl].numpy(), s["camrot"][sl].numpy(), s["focal"][sl].numpy(),
                                s["princpt"][sl].numpy(), s["pixelcoords"][sl].numpy(), s["volradius"])
-        o.march_forward(rp, rd, s["stepsize"], tm, s["primpos"][sl].numpy(), s["primrot"][sl].numpy(),
-                        s["primscale"][sl].numpy(), s["template"][sl].numpy())
+        rgba = o.march_forward(rp, rd, s["stepsize"], tm, s["primpos"][sl].numpy(), s["primrot"][sl].numpy(),
+                               s["primscale"][sl].numpy(), s["template"][sl].numpy())[0]
         calls["n"] += 1
+        return torch.from_numpy(rgba)
 
     step.calls = calls
-    return step, {"n_local": hi - lo, "H": H, "W": W, "K": K, "slab": 8, "N": N}
+    _oracle_step_factory.last_step = step
+    return step, {"n_local": hi - lo, "H": H, "W": W, "K": K, "slab": 8, "N": N,
+                  "outputs": lambda rgba: {"rgba": rgba, "template": s["template"][sl]}}
 
 
 def _worker(rank, world, port, outdir, scaling):
@@ -203,3 +206,32 @@ def test_collectives_of_the_multi_gpu_path_run_through_rccl_on_one_gpu(mode):
         t = j["train"]
         assert t["allreduce_mb"] > 0 and t["final_loss"] == t["final_loss"]      # DDP was on; the loss is finite
         assert t["ddp_bucket_cap_mb"] == (25 if mode == "train_bucket25" else 256)
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path, monkeypatch, capfd):
+    """--dump-outputs DIR: the arrays the step factory names for the last timed step land in DIR/<name>.npy, the same on
+    every run with the same arguments; an array over DUMP_MAX_ELEMS elements is a fixed sample; --steps sets the number of
+    timed steps (the factory counts warm-up + timed calls)."""
+    import numpy as np
+    import bench
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 4000)        # rgba (2 x 16 x 16 x 4 = 2048) whole, template sampled
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        bench.main(["--gpus", "1", "--steps", "4", "--warmup", "2", "--workload", "C1", "--cams", "2", "--dump-outputs", str(d)],
+                   backend="gloo", make_step=_oracle_step_factory, device="cpu")
+        assert _oracle_step_factory.last_step.calls["n"] == 2 + 4
+        j = json.loads(capfd.readouterr().out.strip().splitlines()[-1])
+        assert j["steps"] == 4 and j["dump_outputs"]["dir"] == str(d)
+        arrays = j["dump_outputs"]["arrays"]
+        assert arrays["rgba"] == {"shape": [2, 16, 16, 4], "sampled": None, "dtype": "float32"}
+        assert arrays["template"]["shape"] == [2, 32, 8, 8, 8, 4] and 0 < arrays["template"]["sampled"] <= 4000
+        assert sorted(os.listdir(d)) == ["rgba.npy", "template.npy"]
+        dumps.append({n: np.load(d / (n + ".npy")) for n in ("rgba", "template")})
+    assert dumps[0]["rgba"].shape == (2, 16, 16, 4) and dumps[0]["rgba"].dtype == np.float32
+    assert np.abs(dumps[0]["rgba"]).max() > 0
+    idx = bench.dump_sample_index("template", 2 * 32 * 8 * 8 * 8 * 4)
+    assert dumps[0]["template"].shape == idx.shape
+    for n in ("rgba", "template"):
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n

@@ -60,7 +60,7 @@ def _cos(a, b):
     return float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b) + 1e-300))
 
 
-@pytest.mark.parametrize("fixture", [GOLDEN, GOLDEN_MULTITILE, GOLDEN_RAGGED])
+@pytest.mark.parametrize("fixture", [GOLDEN, GOLDEN_MULTITILE, GOLDEN_RAGGED], ids=os.path.basename)  # ids not tied to the checkout's path
 def test_standin_matches_the_reference_module_on_cpu(fixture):
     m, g = _load("cpu", fixture=fixture)
     bg, grads = _run(m, g, "cpu")

@@ -1,15 +1,16 @@
 """The native-module shims (ava-256_amd/native_shim.py, extensions/*/mvpraymarchlib.py, utilslib.py): positional
-signatures equal to the reference's pybind functions (checked against the mounted .cpp in the build container), and -- on
-the GPU -- the call sequence of the reference's autograd Function reproduces this build's operator path."""
+signatures equal to the reference's pybind functions (their parameter names as declared in the reference's .cpp, stored in
+tests/golden/reference_interfaces.json by tests/golden/gen_reference_interfaces.py), and -- on the GPU -- the call sequence
+of the reference's autograd Function reproduces this build's operator path."""
 import inspect
+import json
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-REF = "/root/reference"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 _RENAME = {"rayposim": "raypos", "raydirim": "raydir", "tminmaxim": "tminmax", "tplate": "template",
            "grad_tplate": "grad_template", "rayrgbaim": "rayrgba", "raysatim": "raysat", "raytermim": "rayterm",
@@ -17,27 +18,21 @@ _RENAME = {"rayposim": "raypos", "raydirim": "raydir", "tminmaxim": "tminmax", "
            "pixelcoordsim": "pixelcoords", "algorithm": "algo", "sortboxes": "sortprims"}
 
 
-def _cpp_params(path, fn):
-    """Ordered parameter names of `fn(...)` as declared in the reference's binding source."""
-    src = open(path).read()
-    m = re.search(r"\b%s\s*\(([^{;]*?)\)\s*\{" % fn, src, re.S)
-    assert m, fn
-    names = []
-    for part in m.group(1).replace("\n", " ").split(","):
-        part = part.split("=")[0].strip()
-        if part:
-            names.append(_RENAME.get(part.split()[-1].lstrip("*&"), part.split()[-1].lstrip("*&")))
-    return names
+def _ref_params(path, fn):
+    """Ordered parameter names of `fn(...)` as declared in the reference's binding source `path`, in this build's spelling."""
+    with open(os.path.join(GOLDEN, "reference_interfaces.json")) as f:
+        b = json.load(f)["bindings"][fn]
+    assert b["file"] == path, (fn, b["file"])
+    return [_RENAME.get(n, n) for n in b["params"]]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference is mounted only in the build container")
 @pytest.mark.parametrize("fn,path", [("compute_aabb", "extensions/mvpraymarch/mvpraymarch.cpp"),
                                      ("raymarch_forward", "extensions/mvpraymarch/mvpraymarch.cpp"),
                                      ("raymarch_backward", "extensions/mvpraymarch/mvpraymarch.cpp"),
                                      ("compute_raydirs_forward", "extensions/utils/utils.cpp")])
 def test_shim_signatures_equal_the_reference_bindings(fn, path):
     from ava256_amd import native_shim
-    ref = _cpp_params(os.path.join(REF, path), fn)
+    ref = _ref_params(path, fn)
     mine = list(inspect.signature(getattr(native_shim, fn)).parameters)
     mine = ["raydir" if n == "raydirs" else n for n in mine]
     assert mine == ref, (fn, mine, ref)

@@ -279,9 +279,12 @@ def test_training_through_the_kernels_reduces_the_loss():
 
 def test_config_reader_takes_the_references_keys(tmp_path):
     """ava-256_amd/config.py reads the keys ddp-train.py reads from configs/config*.yaml (:78,82,321,404-430,441) into the
-    Trainer's arguments; `--opts`-style overrides; unknown loss terms are rejected, other sections ignored.  With the
-    reference mounted (build container) its own three files are read as well."""
+    Trainer's arguments; `--opts`-style overrides; unknown loss terms are rejected, other sections ignored.  The keys this
+    reader takes from the reference's own three files, with their values, are stored in tests/golden/reference_interfaces.json
+    (tests/golden/gen_reference_interfaces.py) and read back through the same reader."""
+    import json
     import os
+    import yaml
     from ava256_amd.config import load_train_config
     from ava256_amd.trainloop import Trainer
     y = tmp_path / "c.yaml"
@@ -300,12 +303,20 @@ def test_config_reader_takes_the_references_keys(tmp_path):
     (tmp_path / "bad.yaml").write_text("train:\n  losses:\n    irgbl1: 1.0\n    vgg: 1.0\n")
     with pytest.raises(NotImplementedError):
         load_train_config(str(tmp_path / "bad.yaml"))
-    for name in ("config.yaml", "config-4.yaml", "config-256.yaml"):
-        p = os.path.join("/root/reference/configs", name)
-        if os.path.exists(p):
-            r = load_train_config(p)
-            assert r["trainer"]["lr"] == 2.0e-4 and r["trainer"]["clip"] == 1.0 and r["batchsize"] >= 1
-            assert set(r["trainer"]["loss_weights"]) <= {"irgbl1", "vertl1", "kldiv", "primvolsum"}
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_interfaces.json")) as f:
+        ref_configs = json.load(f)["configs"]
+    assert sorted(ref_configs) == ["config-256.yaml", "config-4.yaml", "config.yaml"]
+    for name, doc in ref_configs.items():
+        p = tmp_path / name
+        p.write_text(yaml.safe_dump(doc))
+        r = load_train_config(str(p))
+        tr_ref = doc["train"]
+        assert r["trainer"]["lr"] == 2.0e-4 and r["trainer"]["clip"] == 1.0 and r["batchsize"] >= 1
+        assert set(r["trainer"]["loss_weights"]) <= {"irgbl1", "vertl1", "kldiv", "primvolsum"}
+        assert r["trainer"] == {"lr": tr_ref["init_learning_rate"], "lr_scheduler_iter": tr_ref["lr_scheduler_iter"],
+                                "gamma": tr_ref["gamma"], "clip": tr_ref["clip"], "loss_weights": tr_ref["losses"]}
+        assert (r["batchsize"], r["nids"], r["maxiter"], r["num_epochs"]) == (
+            tr_ref["batchsize"], tr_ref["nids"], tr_ref["maxiter"], tr_ref["num_epochs"])
 
 
 def test_matrix_form_of_rodrigues_equals_the_per_element_form():
