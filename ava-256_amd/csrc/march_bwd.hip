@@ -8,18 +8,20 @@
 namespace mvp {
 
 // =================================================================================================
-// Primitive-centric backward.  One workgroup (4 waves) per (image n, primitive k).
+// Primitive-centric backward.  One workgroup (PW = 2 or 3 waves; kPreciseWaves in the two-pass instantiation) per
+// (image n, primitive k).
 //   LDS: [V] float4 template slab | [2][Vp] int64 fixed-point gradient, two channels per word: (r | g), (b | a) |
-//        ray queue (kQueueCap x 8 B) | small reduce area.   Vp = padded voxel count (z stride TH*TW + kGradPadZ, see below;
-//        the warp-field variant has no pad: a cell index serves the slab read and its scatter) | warp-field variant only:
+//        ray queue (kQueueCap x 8 B) | reduce area (64 floats + 16 B) | kLenBuckets int32 | list ranks (2 B per list slot).
+//        Vp = padded voxel count (z stride TH*TW + kGradPadZ, see below; the warp-field variant has no pad: a cell index
+//        serves the slab read and its scatter) | warp-field variant only, at prim_lds_base (16-byte aligned):
 //        [VW] float4 warp grid | [VW] int64 (x | y) + [VW] int32 z fixed-point sums of grad_warp.
-//   Work proceeds in rounds of 8 list entries (ray packets):
+//   Work proceeds in rounds of up to PW * kEntriesPerWave list entries (ray packets):
 //     phase 1 (lanes = the rays the round's list records NAME -- each record carries the forward's mask of the packet's rays
 //             that have a lattice step in this box, ~40 % of them on head-like scenes; a wave compacts the rays its records
 //             name and examines them 64 at a time, round 6): exact ray/box interval, clipped to the ray's first step and to
 //             the sample that saturated it -> the rays that really have samples here go into the LDS queue, sorted by
 //             their number of steps (LDS integer atomics for bucket tickets).
-//     phase 2 (lanes = queued rays, evenly split over the 4 waves): every lane walks ITS OWN lattice steps
+//     phase 2 (lanes = queued rays, evenly split over the PW waves): every lane walks ITS OWN lattice steps
 //             through the box (aligned by entry step), samples the LDS slab, scatters into the LDS gradient.
 // Per-sample math: primaccum.h:81-98 with the prefix replaced by the forward's record
 //   key <  satkey : weight = alpha*dt, dL_alpha = dt * dot((rgb,1) - (raysat,1 | 0), dL)
@@ -164,6 +166,9 @@ __device__ __forceinline__ int fix_rn(float v) {
     asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(v));
     return r;
 }
+// Two fixed-point sums per 64-bit LDS atomic: word = hi * 2^32 + lo (signed lo): low dword lo, high dword hi + (lo >> 31).
+// (The encoders that use it stay macros at their call sites: as functions they change the scatter's code -- see there.)
+#define MVP_PACK2(LO_, HI_) ((unsigned long long)(uint32_t)(LO_) | ((unsigned long long)(uint32_t)((HI_) + ((LO_) >> 31)) << 32))
 
 // (WARP, round 6: the zero padding is evaluated without branches, as zero weights on cells the sample reads anyway --
 //  march_common.h: tri_zero_pad.)
@@ -719,21 +724,9 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
                     // sums are packed two per 64-bit atomic: (r | g), (b | a) per slab cell, (x | y) + z per warp node:
                     // 16 + 16 LDS atomics per sample.
                     if (inside) {
-                        float fade;
-                        f3 ypow;
-                        if (FADE8) {
-                            const f3 y2 = y * y, y4 = y2 * y2;
-                            fade = fast_exp2(nfs_log2e * (y4.x * y4.x + y4.y * y4.y + y4.z * y4.z));
-                            ypow = y4 * y2 * y;
-                        } else {
-                            const f3 ay = mk3(fabsf(y.x), fabsf(y.y), fabsf(y.z));
-                            fade = fast_exp(-p.fadescale * (fast_pow(ay.x, p.fadeexp) + fast_pow(ay.y, p.fadeexp) +
-                                                            fast_pow(ay.z, p.fadeexp)));
-                            const float e1 = p.fadeexp - 1.f;
-                            ypow = mk3(fast_pow(ay.x, e1) * (y.x > 0.f ? 1.f : -1.f),
-                                       fast_pow(ay.y, e1) * (y.y > 0.f ? 1.f : -1.f),
-                                       fast_pow(ay.z, e1) * (y.z > 0.f ? 1.f : -1.f));
-                        }
+                        const float fsum = fade_sum<FADE8>(y, p.fadeexp);
+                        const float fade = FADE8 ? fast_exp2(nfs_log2e * fsum) : fast_exp(-p.fadescale * fsum);
+                        const f3 ypow = fade_slope<FADE8>(y, p.fadeexp);
                         // (1) y1 = warp(y).  y is strictly inside: every corner of the warp grid is in bounds once the base corner
                         //     is clamped (the plain sampler's form: one fma per index axis, float base corner, one conversion)
                         const float iwx = fmaf(y.x, mwx, mwx), iwy = fmaf(y.y, mwy, mwy), iwz = fmaf(y.z, mwz, mwz);
@@ -769,64 +762,22 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
                         y1z = fmaf(n111q.z, U11.y, y1z);
                         // (2) the slab at y1 with the reference's zero padding (y1 may leave the slab)
                         const TriZ tt = tri_zero_pad(mk3(y1l.x, y1l.y, y1z), TD, TH, TW);
-#define MVP_LOADC(NAME_, IDX_)              \
-    const float4 NAME_##q = s_T[IDX_];      \
-    const v2f NAME_##l = {NAME_##q.x, NAME_##q.y}, NAME_##h = {NAME_##q.z, NAME_##q.w};
-                        MVP_LOADC(c000, tt.c[0])
-                        MVP_LOADC(c001, tt.c[1])
-                        MVP_LOADC(c010, tt.c[2])
-                        MVP_LOADC(c011, tt.c[3])
-                        MVP_LOADC(c100, tt.c[4])
-                        MVP_LOADC(c101, tt.c[5])
-                        MVP_LOADC(c110, tt.c[6])
-                        MVP_LOADC(c111, tt.c[7])
-#undef MVP_LOADC
-                        v2f vl = pk_mul_lo(c000l, tt.W00), vh = pk_mul_lo(c000h, tt.W00);
-                        vl = pk_fma_hi(c001l, tt.W00, vl), vh = pk_fma_hi(c001h, tt.W00, vh);
-                        vl = pk_fma_lo(c010l, tt.W01, vl), vh = pk_fma_lo(c010h, tt.W01, vh);
-                        vl = pk_fma_hi(c011l, tt.W01, vl), vh = pk_fma_hi(c011h, tt.W01, vh);
-                        vl = pk_fma_lo(c100l, tt.W10, vl), vh = pk_fma_lo(c100h, tt.W10, vh);
-                        vl = pk_fma_hi(c101l, tt.W10, vl), vh = pk_fma_hi(c101h, tt.W10, vh);
-                        vl = pk_fma_lo(c110l, tt.W11, vl), vh = pk_fma_lo(c110h, tt.W11, vh);
-                        vl = pk_fma_hi(c111l, tt.W11, vl), vh = pk_fma_hi(c111h, tt.W11, vh);
+                        Corners8 C;
+                        C.set(0, s_T[tt.c[0]]), C.set(1, s_T[tt.c[1]]), C.set(2, s_T[tt.c[2]]), C.set(3, s_T[tt.c[3]]);
+                        C.set(4, s_T[tt.c[4]]), C.set(5, s_T[tt.c[5]]), C.set(6, s_T[tt.c[6]]), C.set(7, s_T[tt.c[7]]);
                         // (a sample whose y1 has an axis entirely outside the slab has eight zero weights and -- this kernel
                         //  marches finite slabs only -- the value 0, like the reference's empty sum)
-                        float4 v;
-                        v.x = vl.x, v.y = vl.y, v.z = vh.x, v.w = vh.y;
+                        const float4 v = C.interp(tt.W00, tt.W01, tt.W10, tt.W11);
                         const float alpha = v.w * fade;
                         const bool issat = key == satkey;
                         const float weight = issat ? (1.f - wbefore) : alpha * dt;
                         wbad = wbad || !(fabsf(weight) <= wmax);
                         float4 dLs;
-                        dLs.x = weight * dL3.x;
-                        dLs.y = weight * dL3.y;
-                        dLs.z = weight * dL3.z;
-                        dLs.w = issat ? 0.f
-                                      : dt * ((v.x - (has_sat ? rsat.x : 0.f)) * dL3.x +
-                                              (v.y - (has_sat ? rsat.y : 0.f)) * dL3.y +
-                                              (v.z - (has_sat ? rsat.z : 0.f)) * dL3.z + (has_sat ? 0.f : dLw));
-                        const float gf = -(p.fadescale * p.fadeexp) * alpha * dLs.w;
-                        f3 gy = ypow * gf;
-                        dLs.w *= fade;
+                        sample_dls(dLs, weight, issat, v, dt, dL3, dLw, rsat, has_sat);
+                        f3 gy = fade_grad(dLs, alpha, fade, ypow, p.fadescale, p.fadeexp);
                         const v2f dl = {dLs.x, dLs.y}, dh = {dLs.z, dLs.w};
-#define MVP_DOT4(NAME_, C_)                                 \
-    float NAME_;                                            \
-    {                                                       \
-        const v2f p_ = C_##l * dl + C_##h * dh;             \
-        NAME_ = p_.x + p_.y;                                \
-    }
-                        MVP_DOT4(d000, c000)
-                        MVP_DOT4(d001, c001)
-                        MVP_DOT4(d010, c010)
-                        MVP_DOT4(d011, c011)
-                        MVP_DOT4(d100, c100)
-                        MVP_DOT4(d101, c101)
-                        MVP_DOT4(d110, c110)
-                        MVP_DOT4(d111, c111)
-#undef MVP_DOT4
-                        const f3 gi1 = posgrad_zero_pad(tt, d000, d001, d010, d011, d100, d101, d110, d111);
-// two sums per 64-bit atomic: word = hi * 2^32 + lo (signed lo).  Pass B of a two-pass round adds what pass A rounded away.
-#define MVP_PACK2W(LO_, HI_) ((unsigned long long)(uint32_t)(LO_) | ((unsigned long long)(uint32_t)((HI_) + ((LO_) >> 31)) << 32))
+                        const f3 gi1 = posgrad_zero_pad(tt, C.dot(0, dl, dh), C.dot(1, dl, dh), C.dot(2, dl, dh), C.dot(3, dl, dh),
+                                                        C.dot(4, dl, dh), C.dot(5, dl, dh), C.dot(6, dl, dh), C.dot(7, dl, dh));
 #define MVP_FIXP(PTR_, VLO_, VHI_)                                          \
     {                                                                       \
         const float xl_ = (VLO_), xh_ = (VHI_);                             \
@@ -835,7 +786,7 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
             lo_ = fix_rn((xl_ - (float)lo_) * res_mul);                     \
             hi_ = fix_rn((xh_ - (float)hi_) * res_mul);                     \
         }                                                                   \
-        atomicAdd((PTR_), MVP_PACK2W(lo_, hi_));                            \
+        atomicAdd((PTR_), MVP_PACK2(lo_, hi_));                            \
     }
 #define MVP_FIXS(PTR_, V_)                                                  \
     {                                                                       \
@@ -888,7 +839,6 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
                         }
 #undef MVP_FIXS
 #undef MVP_FIXP
-#undef MVP_PACK2W
                         {  // d(warp lookup)/d(index) for the node values dotted with dL/dy1: the plain sampler's tree
 #define MVP_DOT3(NAME_, N_) const float NAME_ = fmaf(N_##q.z, g1.z, fmaf(N_##q.y, g1.y, N_##q.x * g1.x));
                             MVP_DOT3(e000, n000)
@@ -915,21 +865,9 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
                     continue;
                 }
                 if (inside) {
-                    float fade;
-                    f3 ypow;
-                    if (FADE8) {
-                        const f3 y2 = y * y, y4 = y2 * y2;
-                        fade = fast_exp2(nfs_log2e * (y4.x * y4.x + y4.y * y4.y + y4.z * y4.z));  // exp(-fadescale * sum y^8)
-                        ypow = y4 * y2 * y;
-                    } else {
-                        const f3 ay = mk3(fabsf(y.x), fabsf(y.y), fabsf(y.z));
-                        fade = fast_exp(-p.fadescale * (fast_pow(ay.x, p.fadeexp) + fast_pow(ay.y, p.fadeexp) +
-                                                        fast_pow(ay.z, p.fadeexp)));
-                        const float e1 = p.fadeexp - 1.f;
-                        ypow = mk3(fast_pow(ay.x, e1) * (y.x > 0.f ? 1.f : -1.f),
-                                   fast_pow(ay.y, e1) * (y.y > 0.f ? 1.f : -1.f),
-                                   fast_pow(ay.z, e1) * (y.z > 0.f ? 1.f : -1.f));
-                    }
+                    const float fsum = fade_sum<FADE8>(y, p.fadeexp);
+                    const float fade = FADE8 ? fast_exp2(nfs_log2e * fsum) : fast_exp(-p.fadescale * fsum);
+                    const f3 ypow = fade_slope<FADE8>(y, p.fadeexp);
                     // (y + 1) / 2 * (T - 1) as ONE fma per axis (the forward's three roundings are not needed here: the
                     //  gradient is that of the same trilinear polynomial, evaluated at a point 1 ulp away at most)
                     const float ix = fmaf(y.x, mx, mx), iy = fmaf(y.y, my, my), iz = fmaf(y.z, mz, mz);
@@ -942,7 +880,9 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
                     const float vbf = fmaf(fz0, (float)sD, fmaf(fy0, (float)sH, fx0));  // (small integers: exact; sW = 1)
                     const int vb = (int)vbf;
                     // Corner values are kept as the (x,y) / (z,w) register pairs the 16-byte LDS reads deliver, so that
-                    // interpolation and the 8 dot products below are packed-fp32 instructions on natural pairs.
+                    // interpolation and the 8 dot products below are packed-fp32 instructions on natural pairs.  (The same
+                    // arithmetic as march_common.h's Corners8 and the warp body's node tree, written out here, like the
+                    // fixed-point encoders: as those helpers they change this kernel's generated code.)
 #define MVP_LOADC(NAME_, IDX_)              \
     const float4 NAME_##q = s_T[IDX_];      \
     const v2f NAME_##l = {NAME_##q.x, NAME_##q.y}, NAME_##h = {NAME_##q.z, NAME_##q.w};
@@ -975,16 +915,8 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
                     const float weight = issat ? (1.f - wbefore) : alpha * dt;
                     wbad = wbad || !(fabsf(weight) <= wmax);  // outside the fixed-point bound (signed opacity) or NaN
                     float4 dLs;
-                    dLs.x = weight * dL3.x;
-                    dLs.y = weight * dL3.y;
-                    dLs.z = weight * dL3.z;
-                    dLs.w = issat ? 0.f
-                                  : dt * ((v.x - (has_sat ? rsat.x : 0.f)) * dL3.x +
-                                          (v.y - (has_sat ? rsat.y : 0.f)) * dL3.y +
-                                          (v.z - (has_sat ? rsat.z : 0.f)) * dL3.z + (has_sat ? 0.f : dLw));
-                    const float gf = -(p.fadescale * p.fadeexp) * alpha * dLs.w;
-                    f3 gy = ypow * gf;
-                    dLs.w *= fade;
+                    sample_dls(dLs, weight, issat, v, dt, dL3, dLw, rsat, has_sat);
+                    f3 gy = fade_grad(dLs, alpha, fade, ypow, p.fadescale, p.fadeexp);
                     const v2f dl = {dLs.x, dLs.y}, dh = {dLs.z, dLs.w};
 #define MVP_DOT4(NAME_, C_)                                 \
     float NAME_;                                            \
@@ -1021,8 +953,6 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
                         const v2f qxy = {dLs.x * s_rgb, dLs.y * s_rgb}, qzw = {dLs.z * s_rgb, dLs.w * s_a};
                         const int gb = (int)fmaf(fz0, (float)(gD - sD), vbf);  // z0 * gD + y0 * gH + x0 (gH = sH)
                         unsigned long long *Ap = reinterpret_cast<unsigned long long *>(s_acc) + gb;
-// two channels per 64-bit atomic: word = hi * 2^32 + lo (signed lo): low dword lo, high dword hi + (lo >> 31)
-#define MVP_PACK2(LO_, HI_) ((unsigned long long)(uint32_t)(LO_) | ((unsigned long long)(uint32_t)((HI_) + ((LO_) >> 31)) << 32))
 #define MVP_FIX1(OFF_, VLO_, VHI_)                                                    \
     {                                                                                 \
         const int lo_ = fix_rn(VLO_), hi_ = fix_rn(VHI_);                             \
@@ -1059,7 +989,6 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
 #undef MVP_LSCATTER
 #undef MVP_FIX1B
 #undef MVP_FIX1
-#undef MVP_PACK2
                     }
                     // xmt = (o - pos) + d * t is affine in t along this ray: keep sum(gy) and sum(t * gy) only
                     ra0 += gy.x, ra1 += gy.y, ra2 += gy.z;
@@ -1290,13 +1219,13 @@ extern "C" int mvp_march_backward(int N, int H, int W, int K, const float *raypo
     if (!norays && (!raysat || !grad_rayrgba || !aligned16(grad_rayrgba))) return MVP_ERR_BADARG;
     const size_t padz = warp ? 0 : kGradPadZ;  // (bwd_prim_body: kPadZ)
     const size_t Vp = (size_t)TD * ((size_t)TH * TW + padz);
-    // float4 slab + [4][Vp] int32 + ray queue + reduce area (+ queue tail)
+    // float4 slab + [2][Vp] int64 + ray queue + reduce area + length buckets
     // 2 or 3 waves per workgroup by the work a primitive has: ray packets per primitive (see the note at kEntriesPerWave)
     const int pw = ((long long)p.tiles_x * p.tiles_y * 4 > 5ll * K) ? 3 : 2;
     // + list indices by rank (2 bytes per list slot; used by primitives whose list needs more than one round)
     size_t lds = V * 16 + Vp * 16 + (size_t)prim_queue_cap(pw) * 8 + 64 * sizeof(float) + 16 + kLenBuckets * 4 +
                  (((size_t)(primlist_cap > 0 ? primlist_cap : 0) * 2 + 15) & ~(size_t)15);
-    if (warp) {  // + the warp grid (float4 per node) and its [3][VWp] accumulators
+    if (warp) {  // + the warp grid (float4 per node) and its accumulators: [VWp] int64 (x | y) + [VWp] int32 z
         lds = (lds + 15) & ~(size_t)15;
         p.prim_lds_base = (int)lds;
         const size_t VW = (size_t)WD * WH * WW, VWp = (size_t)WD * ((size_t)WH * WW + padz);

@@ -663,15 +663,75 @@ __device__ __forceinline__ float4 sample_warped(const float *__restrict__ Wk, co
     v.w = v.w * fade;
     return v;
 }
+// ---- per-sample pieces of the backward, shared by the primitive-centric body (march_bwd.hip) and the ray-centric one
+//      (march_packet.h).  The forward samplers above pin their own arithmetic and do not use them.
+// The fade exp(-fadescale * sum_i |y_i|^e), e = 8 for FADE8, else fadeexp (primsampler.h:48-51): fade_sum is the sum, the
+// caller takes the exponential.  fade_slope is |y|^(e-1) * sgn(y), the fade's slope up to the factor -fadescale * e
+// (primsampler.h:70-76).  (Two functions, called in this order: one that returns both schedules the ray-centric body
+// differently.)
 template <bool FADE8>
-__device__ __forceinline__ float fade_of(f3 y, float fadescale, float fadeexp) {
+__device__ __forceinline__ float fade_sum(f3 y, float fadeexp) {
     if (FADE8) {
         const f3 y2 = y * y, y4 = y2 * y2;
-        return fast_exp(-fadescale * (y4.x * y4.x + y4.y * y4.y + y4.z * y4.z));
+        return y4.x * y4.x + y4.y * y4.y + y4.z * y4.z;
     }
-    return fast_exp(-fadescale *
-                    (fast_pow(fabsf(y.x), fadeexp) + fast_pow(fabsf(y.y), fadeexp) + fast_pow(fabsf(y.z), fadeexp)));
+    return fast_pow(fabsf(y.x), fadeexp) + fast_pow(fabsf(y.y), fadeexp) + fast_pow(fabsf(y.z), fadeexp);
 }
+template <bool FADE8>
+__device__ __forceinline__ f3 fade_slope(f3 y, float fadeexp) {
+    if (FADE8) {
+        const f3 y2 = y * y, y4 = y2 * y2;
+        return y4 * y2 * y;
+    }
+    const float e1 = fadeexp - 1.f;
+    return mk3(fast_pow(fabsf(y.x), e1) * (y.x > 0.f ? 1.f : -1.f), fast_pow(fabsf(y.y), e1) * (y.y > 0.f ? 1.f : -1.f),
+               fast_pow(fabsf(y.z), e1) * (y.z > 0.f ? 1.f : -1.f));
+}
+// dL/d(sample) = (w dL_rgb, dL_alpha), primaccum.h:81-98.  issat: this is the sample that saturated the ray (dL_alpha = 0);
+// rsat / has_sat: the colour of that sample and whether the ray has one.
+__device__ __forceinline__ void sample_dls(float4 &dLs, float weight, bool issat, float4 v, float dt, f3 dL3, float dLw,
+                                           f3 rsat, bool has_sat) {
+    dLs.x = weight * dL3.x;
+    dLs.y = weight * dL3.y;
+    dLs.z = weight * dL3.z;
+    dLs.w = issat ? 0.f
+                  : dt * ((v.x - (has_sat ? rsat.x : 0.f)) * dL3.x + (v.y - (has_sat ? rsat.y : 0.f)) * dL3.y +
+                          (v.z - (has_sat ? rsat.z : 0.f)) * dL3.z + (has_sat ? 0.f : dLw));
+}
+// primsampler.h:70-76: the fade's share of dL/dy; dLs.w becomes dL/d(template alpha)
+__device__ __forceinline__ f3 fade_grad(float4 &dLs, float alpha, float fade, f3 ypow, float fadescale, float fadeexp) {
+    const float gf = -(fadescale * fadeexp) * alpha * dLs.w;
+    const f3 gy = ypow * gf;
+    dLs.w *= fade;
+    return gy;
+}
+// The eight corner cells of a trilinear lookup as the 16-byte LDS reads deliver them, used as (x,y) / (z,w) register pairs,
+// so that interpolation and the dot products with dL are packed-fp32 instructions on natural pairs.
+struct Corners8 {
+    v2f l[8], h[8];  // corners 000, 001 (x + 1), 010 (y + 1), ..., 111
+    __device__ __forceinline__ void set(int i, float4 q) { l[i] = v2f{q.x, q.y}, h[i] = v2f{q.z, q.w}; }
+    __device__ __forceinline__ v2f lo(int i) const { return l[i]; }
+    __device__ __forceinline__ v2f hi(int i) const { return h[i]; }
+    // sum_c w_c * c on the natural weight pairs W_zy = (w_zy0, w_zy1) (tri_interp's TriF form)
+    __device__ __forceinline__ float4 interp(v2f W00, v2f W01, v2f W10, v2f W11) const {
+        v2f vl = pk_mul_lo(lo(0), W00), vh = pk_mul_lo(hi(0), W00);
+        vl = pk_fma_hi(lo(1), W00, vl), vh = pk_fma_hi(hi(1), W00, vh);
+        vl = pk_fma_lo(lo(2), W01, vl), vh = pk_fma_lo(hi(2), W01, vh);
+        vl = pk_fma_hi(lo(3), W01, vl), vh = pk_fma_hi(hi(3), W01, vh);
+        vl = pk_fma_lo(lo(4), W10, vl), vh = pk_fma_lo(hi(4), W10, vh);
+        vl = pk_fma_hi(lo(5), W10, vl), vh = pk_fma_hi(hi(5), W10, vh);
+        vl = pk_fma_lo(lo(6), W11, vl), vh = pk_fma_lo(hi(6), W11, vh);
+        vl = pk_fma_hi(lo(7), W11, vl), vh = pk_fma_hi(hi(7), W11, vh);
+        float4 v;
+        v.x = vl.x, v.y = vl.y, v.z = vh.x, v.w = vh.y;
+        return v;
+    }
+    // corner i dotted with dL = (dl, dh)
+    __device__ __forceinline__ float dot(int i, v2f dl, v2f dh) const {
+        const v2f p = lo(i) * dl + hi(i) * dh;
+        return p.x + p.y;
+    }
+};
 // d(trilinear)/d(position) in index units for channel-dotted corner values `dotc` (utils.h:592-642): returns
 // (sum +-wy*wz*dot, sum +-wx*wz*dot, sum +-wx*wy*dot) over the in-bounds corners
 __device__ __forceinline__ void tri_posgrad_acc(const TriG &t, int c, float dot, f3 &g) {

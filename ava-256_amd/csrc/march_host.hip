@@ -75,7 +75,7 @@ int march_common_checks(bool bwd, mvp::MarchParams &p) {
     }
     if (p.K > 0 && (!p.nodeaabb || !p.primpos || !p.primrot || !p.primscale || !p.tplate)) return MVP_ERR_BADARG;
     if (!aligned16(p.tplate) || (p.tminmax && !aligned16(p.tminmax)) || !aligned16(p.nodeaabb)) return MVP_ERR_BADARG;
-    if (p.pl_cap < 0 || (p.pl_cap & 3)) return MVP_ERR_BADARG;  // (lists are read four entries = 32 bytes at a time)
+    if (p.pl_cap < 0 || (p.pl_cap & 3)) return MVP_ERR_BADARG;  // (lists are read four 16-byte entries = 64 bytes at a time)
     if (p.rayaux && !aligned16(p.rayaux)) return MVP_ERR_BADARG;
     if (p.pl_list && !aligned16(p.pl_list)) return MVP_ERR_BADARG;
     const int rc_grid = setup_block_map(p);

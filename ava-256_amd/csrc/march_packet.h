@@ -95,7 +95,8 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
         const f3 ird = mk3(fast_rcp(d.x), fast_rcp(d.y), fast_rcp(d.z));
         const f3 t0 = mk3((a0.x - o.x) * ird.x, (a0.y - o.y) * ird.y, (a1.x - o.z) * ird.z);
         const f3 t1 = mk3((a1.y - o.x) * ird.x, (a2.x - o.y) * ird.y, (a2.y - o.z) * ird.z);
-        // (a NaN bound or quotient drops out of the min / max, as in packet_hits_box; an all-NaN box fails the comparison)
+        // (a NaN bound or quotient drops out of the min / max, as in packet_hits_box.  An all-NaN box PASSES this test --
+        //  every term drops out, tn = tmin and tf = tmax + 1e-5 --; packet_hits_box's all_nan test is what rejects it)
         const float tn = fmaxf(max3f(fminf(t0.x, t1.x), fminf(t0.y, t1.y), fminf(t0.z, t1.z)), tmin);
         const float tf = fminf(min3f(fmaxf(t0.x, t1.x), fmaxf(t0.y, t1.y), fmaxf(t0.z, t1.z)), tmax + 1e-5f);
         root_any = __ballot(active && tn <= tf + 1e-4f + 1e-5f * fabsf(tf)) != 0ull;
@@ -673,17 +674,8 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
                         f3 gy = mk3(0.f, 0.f, 0.f);  // BWD: dL/dy of this lane's sample (0 when not inside)
                         if (BWD && WARP && inside) {
                             // ---- warp-field sampler, backward (primsampler.h:68-91 with dowarp; utils.h:504-643 twice) ----
-                            const float fade = fade_of<FADE8>(y, p.fadescale, p.fadeexp);
-                            f3 ypow;
-                            if (FADE8) {
-                                const f3 y2 = y * y, y4 = y2 * y2;
-                                ypow = y4 * y2 * y;
-                            } else {
-                                const float e1 = p.fadeexp - 1.f;
-                                ypow = mk3(fast_pow(fabsf(y.x), e1) * (y.x > 0.f ? 1.f : -1.f),
-                                           fast_pow(fabsf(y.y), e1) * (y.y > 0.f ? 1.f : -1.f),
-                                           fast_pow(fabsf(y.z), e1) * (y.z > 0.f ? 1.f : -1.f));
-                            }
+                            const float fade = fast_exp(-p.fadescale * fade_sum<FADE8>(y, p.fadeexp));
+                            const f3 ypow = fade_slope<FADE8>(y, p.fadeexp);
                             const size_t VW3 = (size_t)p.WD * p.WH * p.WW * 3;
                             const float *Wk = p.warp + ((size_t)n * K + k) * VW3;
                             const TriG tw = tri_general(y, p.WD, p.WH, p.WW);
@@ -710,7 +702,8 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
                                 }
                             }
                             const float alpha = v.w * fade;
-                            // ---- primaccum.h:81-98 ----
+                            // ---- primaccum.h:81-98.  (The dL and fade-gradient formulas of march_common.h's sample_dls / fade_grad,
+                            //      written out: called here, those helpers change this kernel's generated code.) ----
                             const float a = alpha * dt;
                             const bool thissat = rgba.w + a >= 1.f;
                             sat = sat || thissat;
@@ -769,23 +762,8 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
                             }
                         } else if (inside) {
                             // ---- fade (primsampler.h:48-51) ----
-                            float fade;
-                            f3 ypow;  // |y|^(fadeexp-1) * sgn(y), backward only
-                            if (FADE8) {
-                                const f3 y2 = y * y, y4 = y2 * y2;
-                                fade = fast_exp(-p.fadescale * (y4.x * y4.x + y4.y * y4.y + y4.z * y4.z));
-                                if (BWD) ypow = y4 * y2 * y;
-                            } else {
-                                const f3 ay = mk3(fabsf(y.x), fabsf(y.y), fabsf(y.z));
-                                fade = fast_exp(-p.fadescale * (fast_pow(ay.x, p.fadeexp) + fast_pow(ay.y, p.fadeexp) +
-                                                                fast_pow(ay.z, p.fadeexp)));
-                                if (BWD) {
-                                    const float e1 = p.fadeexp - 1.f;
-                                    ypow = mk3(fast_pow(ay.x, e1) * (y.x > 0.f ? 1.f : -1.f),
-                                               fast_pow(ay.y, e1) * (y.y > 0.f ? 1.f : -1.f),
-                                               fast_pow(ay.z, e1) * (y.z > 0.f ? 1.f : -1.f));
-                                }
-                            }
+                            const float fade = fast_exp(-p.fadescale * fade_sum<FADE8>(y, p.fadeexp));
+                            const f3 ypow = fade_slope<FADE8>(y, p.fadeexp);
                             // ---- trilinear, align_corners=True (utils.h:414-468).  y strictly inside (-1,1) puts
                             //      i in [0, T-1]; clamping the base corner to T-2 keeps all 8 corners in bounds and
                             //      gives the same value as the reference's zero-padded form (the weight of an
@@ -823,7 +801,7 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
                             const float alpha = v.w * fade;  // primsampler.h:63
 
                             {  // (only the backward instantiation reaches this body; the forward left through pass B above)
-                                // ---- primaccum.h:81-98 ----
+                                // ---- primaccum.h:81-98 (written out: see the warp-field body above) ----
                                 const float a = alpha * dt;
                                 const bool thissat = rgba.w + a >= 1.f;
                                 sat = sat || thissat;
@@ -862,11 +840,11 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
                                 MVP_SCATTER(sD + sH + sW, w111)
     #undef MVP_SCATTER
                                 // ---- utils.h:592-642: d/d(position) ----
-    #define MVP_DOT4(C_) ((C_).x * dLs.x + (C_).y * dLs.y + (C_).z * dLs.z + (C_).w * dLs.w)
-                                const float d000 = MVP_DOT4(c000), d001 = MVP_DOT4(c001), d010 = MVP_DOT4(c010),
-                                            d011 = MVP_DOT4(c011), d100 = MVP_DOT4(c100), d101 = MVP_DOT4(c101),
-                                            d110 = MVP_DOT4(c110), d111 = MVP_DOT4(c111);
-    #undef MVP_DOT4
+    #define MVP_DOTC(C_) ((C_).x * dLs.x + (C_).y * dLs.y + (C_).z * dLs.z + (C_).w * dLs.w)
+                                const float d000 = MVP_DOTC(c000), d001 = MVP_DOTC(c001), d010 = MVP_DOTC(c010),
+                                            d011 = MVP_DOTC(c011), d100 = MVP_DOTC(c100), d101 = MVP_DOTC(c101),
+                                            d110 = MVP_DOTC(c110), d111 = MVP_DOTC(c111);
+    #undef MVP_DOTC
                                 const float gix = wy0 * wz0 * (d001 - d000) + wy1 * wz0 * (d011 - d010) +
                                                   wy0 * wz1 * (d101 - d100) + wy1 * wz1 * (d111 - d110);
                                 const float giy = wx0 * wz0 * (d010 - d000) + wx1 * wz0 * (d011 - d001) +

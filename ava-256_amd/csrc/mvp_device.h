@@ -88,14 +88,6 @@ __device__ __forceinline__ float dpp_f(float v, int which) {
     }
     return __int_as_float(r);
 }
-__device__ __forceinline__ int dpp_i(int i, int which) {
-    switch (which) {
-        case 0: return MVP_DPP_I(i, 0xB1);
-        case 1: return MVP_DPP_I(i, 0x4E);
-        case 2: return MVP_DPP_I(i, 0x141);
-        default: return MVP_DPP_I(i, 0x140);
-    }
-}
 #undef MVP_DPP_I
 __device__ __forceinline__ float rl_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 

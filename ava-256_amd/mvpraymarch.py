@@ -98,7 +98,7 @@ def primlist_capacity(H, W, K, device=None, N=None):
     so a primitive is listed by ~9-10 * packets / K packets; four times that, at least 32.  Afterwards: 1.25 x the measured
     demand (`note_list_demand`: read one call late and without a host synchronisation; outliers clipped, decaying --
     `_ListDemand.note`, `wanted_from_histogram`), kept while the new value is within [0.6, 1] of the one in use so that
-    the allocation size does not flutter.  Multiple of 8 (the library reads lists 32 bytes at a time), at most 2048, and --
+    the allocation size does not flutter.  Multiple of 8 (the library reads lists 64 bytes -- four 16-byte entries -- at a time), at most 2048, and --
     when N is given -- at most what a memory budget of max(128 MiB, 4 KiB per primitive) allows, never below 32: primitives
     over the capacity are handled by the ray-centric kernel, correctly and slowly."""
     packets = ((H + 7) // 8) * ((W + 7) // 8)
