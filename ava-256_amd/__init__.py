@@ -9,7 +9,8 @@ Only what the path needs lives here:
   raymarcher.py    Raymarcher nn.Module                      (reference: models/raymarchers/mvpraymarcher.py:17-54)
   native_shim.py   `mvpraymarchlib` / `utilslib` with the reference's positional signatures (mvpraymarch.cpp:146-405,
                    utils.cpp:46-137) over the C ABI: the reference's unmodified Python glue can bind to this build
-  halfslab.py      opt-in RENDER path over fp16 RGBA slabs (round 5): template_to_half, assemble_template_half, render_half*
+  halfslab.py      fp16 RGBA slabs: the opt-in RENDER path (round 5: template_to_half, assemble_template_half, render_half*)
+                   and TRAINING over them (mvpraymarch_half*, assemble_template_frames_half: fp32 master, fp16 march)
   assemble.py      fused decoder -> raymarch template assembly  (rgb.py:137-143, assembler.py:261)
   placement.py     primitive placement on the mesh, 3 texels per primitive (row N2; assembler.py:118-122,143-206)
   gradclip.py      multi-tensor NaN/Inf masking + gradient clipping (row N4; ddp-train.py:434-441)
@@ -24,6 +25,8 @@ if its tensors are not on a HIP device or if libmvp_gfx950.so has not been built
 from .raydirs import ComputeRaydirs, compute_raydirs  # noqa: F401
 from .mvpraymarch import MVPRaymarch, MVPRaymarchFromCameras, build_accel, mvpraymarch, mvpraymarch_from_cameras  # noqa: F401
 from .raymarcher import Raymarcher  # noqa: F401
+from .halfslab import mvpraymarch_half, mvpraymarch_half_from_cameras, assemble_template_frames_half  # noqa: F401
 
 __all__ = ["compute_raydirs", "ComputeRaydirs", "mvpraymarch", "MVPRaymarch", "build_accel", "Raymarcher",
-           "mvpraymarch_from_cameras", "MVPRaymarchFromCameras"]
+           "mvpraymarch_from_cameras", "MVPRaymarchFromCameras", "mvpraymarch_half", "mvpraymarch_half_from_cameras",
+           "assemble_template_frames_half"]

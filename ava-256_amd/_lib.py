@@ -40,12 +40,23 @@ SIGNATURES["mvp_march_forward_cams"] = (_c_int, [_c_int] * 4 + [_c_void_p] * 5 +
 SIGNATURES["mvp_march_render_half"] = (_c_int, [_c_int] * 4 + [_c_void_p] * 8 + [_c_float] * 2 + [_c_void_p] * 4 + [_c_int] * 3 +
                                        [_c_void_p] * 2 + [_c_float] * 2 + [_c_void_p] * 2)
 SIGNATURES["mvp_template_to_half"] = (_c_int, [ctypes.c_longlong] + [_c_void_p] * 3)
+# the training path over fp16 slabs: mvp_march_forward / mvp_march_forward_cams / mvp_march_backward without the warp field
+# N,H,W,K | raypos,raydir | stepsize | tminmax,nodeaabb,primpos,primrot,primscale | TD,TH,TW |
+# tplate_half,rayrgba,raysat,rayaux,primlist_count,primlist | primlist_cap | fadescale,fadeexp | diag,stream
+SIGNATURES["mvp_march_forward_half"] = (_c_int, [_c_int] * 4 + [_c_void_p] * 2 + [_c_float] + [_c_void_p] * 5 + [_c_int] * 3 +
+                                        [_c_void_p] * 6 + [_c_int] + [_c_float] * 2 + [_c_void_p] * 2)
+SIGNATURES["mvp_march_forward_cams_half"] = SIGNATURES["mvp_march_forward_cams"]
+# ... | TD,TH,TW | tplate_half,raysat,rayaux,primlist_count,primlist | primlist_cap |
+# grad_rayrgba,g_pos,g_rot,g_scale,g_tplate | fadescale,fadeexp | diag,stream
+SIGNATURES["mvp_march_backward_half"] = (_c_int, [_c_int] * 4 + [_c_void_p] * 2 + [_c_float] + [_c_void_p] * 5 + [_c_int] * 3 +
+                                         [_c_void_p] * 5 + [_c_int] + [_c_void_p] * 5 + [_c_float] * 2 + [_c_void_p] * 2)
 SIGNATURES["mvp_template_assemble_forward_half"] = (_c_int, [_c_int] * 3 + [_c_void_p] * 4)
 SIGNATURES["mvp_template_assemble_forward"] = (_c_int, [_c_int] * 3 + [_c_void_p] * 4)
 SIGNATURES["mvp_template_assemble_backward"] = (_c_int, [_c_int] * 3 + [_c_void_p] * 5)
 # nh,B -> blocks | F,nh,B | tex,opacity,gain | tplate | stream | F,nh,B | tex,opacity,gain,grad_tplate | gtex,gop,partials | stream
 SIGNATURES["mvp_template_assemble_frames_blocks"] = (ctypes.c_longlong, [_c_int] * 2)
 SIGNATURES["mvp_template_assemble_frames_forward"] = (_c_int, [_c_int] * 3 + [_c_void_p] * 5)
+SIGNATURES["mvp_template_assemble_frames_forward_half"] = (_c_int, [_c_int] * 3 + [_c_void_p] * 5)
 SIGNATURES["mvp_template_assemble_frames_backward"] = (_c_int, [_c_int] * 3 + [_c_void_p] * 8)
 # N,K,rw | pos0,sn | rot0,sn | scale0,sn,sk,sc | posres,sn | rotres,sn | scaleres,sn | outputs / gradients | stream
 _POSE_IN = [_c_int, _c_int, ctypes.c_float, _c_void_p, ctypes.c_longlong, _c_void_p, ctypes.c_longlong, _c_void_p,

@@ -141,6 +141,23 @@ __global__ __launch_bounds__(256) void assemble_frames_fwd_kernel(int F, int nh,
     }
 }
 
+// The same frames written as fp16 RGBA slabs (the shadow of the half-slab training path, halfslab.mvpraymarch_half):
+// gain[f] * v in fp32, then rounded to nearest even -- bit for bit the fp32 kernel's output cast to fp16.
+__global__ __launch_bounds__(256) void assemble_frames_fwd_half_kernel(int F, int nh, int B, const float *__restrict__ tex,
+                                                                       const float *__restrict__ opac,
+                                                                       const float *__restrict__ gain,
+                                                                       h4 *__restrict__ tplate) {
+    Texel t;
+    if (!texel_of_thread(nh, B, (int)blockIdx.z, t)) return;
+    const float4 v = texel_value(tex, opac, t);
+    const size_t fstride = (size_t)nh * nh * B * B * B;
+    h4 *out = tplate + t.vo;
+    for (int f = 0; f < F; ++f, out += fstride) {
+        const float s = gain[f];
+        *out = to_half4(make_float4(s * v.x, s * v.y, s * v.z, s * v.w));
+    }
+}
+
 __global__ __launch_bounds__(256) void assemble_frames_bwd_kernel(int F, int nh, int B, const float *__restrict__ tex,
                                                                   const float *__restrict__ opac,
                                                                   const float *__restrict__ gain,
@@ -243,6 +260,22 @@ extern "C" int mvp_template_assemble_frames_forward(int F, int nh, int B, const 
     const int bx = assemble_block(S);
     const dim3 grid((unsigned)((S + bx - 1) / bx), (unsigned)S, (unsigned)B);
     hipLaunchKernelGGL(assemble_frames_fwd_kernel, grid, dim3(bx), 0, (hipStream_t)stream, F, nh, B, tex, opacity, gain, tplate);
+    return launch_status();
+}
+
+extern "C" int mvp_template_assemble_frames_forward_half(int F, int nh, int B, const float *tex, const float *opacity,
+                                                         const float *gain, void *tplate_half, void *stream) {
+    using namespace mvp;
+    int rc = assemble_args_ok(F, nh, B);
+    if (rc != MVP_OK) return rc;
+    const long long S = (long long)nh * B;
+    if ((long long)F * B * S == 0) return MVP_OK;
+    if (!tex || !opacity || !gain || !tplate_half || !aligned16(tplate_half)) return MVP_ERR_BADARG;
+    if (B > 65535 || S > 65535) return MVP_ERR_UNSUPPORTED;
+    const int bx = assemble_block(S);
+    const dim3 grid((unsigned)((S + bx - 1) / bx), (unsigned)S, (unsigned)B);
+    hipLaunchKernelGGL(assemble_frames_fwd_half_kernel, grid, dim3(bx), 0, (hipStream_t)stream, F, nh, B, tex, opacity, gain,
+                       reinterpret_cast<h4 *>(tplate_half));
     return launch_status();
 }
 

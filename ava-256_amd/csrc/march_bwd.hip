@@ -178,9 +178,12 @@ __device__ __forceinline__ int fix_rn(float v) {
 // fixed-point accumulators (grad_warp); the template is sampled at warp(y) with zero padding (general strides only).
 constexpr int kBwdOcc = 3;  // waves per SIMD the register allocation aims at (4 = at most 128 VGPRs: 20 spilled)
 // RESID: the two-pass instantiation (header, DYNAMIC RANGE): owns the primitives the plain one marked, nothing else.
-template <bool FADE8, int TS, int PW, bool WARP, bool RESID>
+// HSLAB: p.tplate holds fp16 RGBA slabs (8 bytes per voxel, 8^3): staged widened to fp32, so the LDS slab -- and everything
+// after staging, the bounds included -- is what the fp32 instantiation sees on template_half.float().
+template <bool FADE8, int TS, int PW, bool WARP, bool RESID, bool HSLAB = false>
 __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int block, float4 *smem4) {
     static_assert(!WARP || TS == 0, "the warp-field variant uses run-time slab dimensions");
+    static_assert(!HSLAB || !WARP, "fp16 slabs: no warp field");
     constexpr int kPrimWaves = PW, kPrimBlock = PW * 64;
     constexpr int kEntriesPerRound = prim_entries_per_round(PW), kQueueCap = prim_queue_cap(PW);
     const int TD = TS ? TS : p.TD, TH = TS ? TS : p.TH, TW = TS ? TS : p.TW;
@@ -232,10 +235,15 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
     const float4 *T4 = reinterpret_cast<const float4 *>(p.tplate) + pk * (size_t)V;
     constexpr int kVoxPerThread = (512 + kPrimBlock - 1) / kPrimBlock;  // 8^3 slab: voxels staged per thread
     float4 tv[kVoxPerThread];
+    const hvox *Th4 = reinterpret_cast<const hvox *>(p.tplate) + pk * (size_t)V;  // (HSLAB)
     if (TS == 8) {
 #pragma unroll
-        for (int i = 0; i < kVoxPerThread; ++i)
-            tv[i] = (tid + i * kPrimBlock < 512) ? MVP_STREAM_LOAD(T4 + tid + i * kPrimBlock) : make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int i = 0; i < kVoxPerThread; ++i) {
+            if constexpr (HSLAB)
+                tv[i] = (tid + i * kPrimBlock < 512) ? widen_vox(Th4[tid + i * kPrimBlock]) : make_float4(0.f, 0.f, 0.f, 0.f);
+            else
+                tv[i] = (tid + i * kPrimBlock < 512) ? MVP_STREAM_LOAD(T4 + tid + i * kPrimBlock) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
     }
     float4 *gT4 = reinterpret_cast<float4 *>(p.grad_tplate) + pk * (size_t)V;
     const uint4 *list = p.pl_list + pk * (size_t)p.pl_cap;  // {key, step range, ray mask lo, hi} per entry
@@ -275,7 +283,7 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
             }
         } else {
             for (int v = tid; v < V; v += kPrimBlock) {
-                const float4 t = T4[v];
+                const float4 t = HSLAB ? widen_vox(Th4[v]) : T4[v];
                 s_T[v] = t;
                 tmaxb = max(tmaxb, max(max(abs_bits(t.x), abs_bits(t.y)), abs_bits(t.z)));
                 amaxb = max(amaxb, abs_bits(t.w));
@@ -1143,6 +1151,13 @@ __global__ __launch_bounds__(PW * 64, WARP ? 2 : kBwdOcc) void bwd_prim_kernel(c
     bwd_prim_body<FADE8, TS, PW, WARP, false>(p, (int)blockIdx.x, smem4);
 }
 
+// The same over fp16 slabs (8^3, no warp field)
+template <bool FADE8, int PW>
+__global__ __launch_bounds__(PW * 64, kBwdOcc) void bwd_prim_hslab_kernel(const MarchParams p) {
+    extern __shared__ __attribute__((aligned(16))) float4 smem4[];
+    bwd_prim_body<FADE8, 8, PW, false, false, true>(p, (int)blockIdx.x, smem4);
+}
+
 // The two-pass instantiation (general slab strides): a small persistent grid that walks the same block -> primitive
 // map and works only on the primitives the kernel above marked; returns at once when it marked none.  kPreciseWaves waves per
 // workgroup: the marked primitives are few and LARGE (tens of thousands of samples each, marched twice), one per workgroup
@@ -1182,19 +1197,56 @@ __global__ __launch_bounds__(kPreciseWaves * 64, WARP ? 1 : 2) void bwd_prim_pre
     }
 }
 
+// ... over fp16 slabs (staged widened: bwd_prim_body's HSLAB)
+template <bool FADE8>
+__global__ __launch_bounds__(kPreciseWaves * 64, 2) void bwd_prim_precise_hslab_kernel(const MarchParams p, const int total_blocks) {
+    extern __shared__ __attribute__((aligned(16))) float4 smem4[];
+    if ((p.pl_count[(size_t)p.N * p.K] & kFlagBwdPrecise) == 0u) return;
+    // Which of this workgroup's blocks are marked: all its counters are looked at in ONE parallel sweep (the body's own test is a
+    // dependent global load + a barrier per block: ~160 blocks x ~2 us per workgroup at C2 when one or two of them have work)
+    constexpr int kTodo = 256;
+    __shared__ int s_todo[kTodo];
+    __shared__ int s_ntodo;
+    if (threadIdx.x == 0) s_ntodo = 0;
+    __syncthreads();
+    for (int b = (int)blockIdx.x + (int)threadIdx.x * (int)gridDim.x; b < total_blocks; b += (int)(blockDim.x * gridDim.x)) {
+        int n, k;
+        if (!prim_of_block(p, b, n, k)) continue;
+        const uint32_t c = p.pl_count[(size_t)n * p.K + k];
+        if ((c & (kCountPrecise | kCountDead)) != kCountPrecise) continue;
+        const int slot = atomicAdd(&s_ntodo, 1);
+        if (slot < kTodo) s_todo[slot] = b;
+    }
+    __syncthreads();
+    const int ntodo = s_ntodo;
+    if (ntodo > kTodo) {  // (more marked blocks than the table holds: the plain walk)
+        for (int b = (int)blockIdx.x; b < total_blocks; b += (int)gridDim.x) {
+            bwd_prim_body<FADE8, 0, kPreciseWaves, false, true, true>(p, b, smem4);
+            __syncthreads();
+        }
+        return;
+    }
+    for (int i = 0; i < ntodo; ++i) {
+        bwd_prim_body<FADE8, 0, kPreciseWaves, false, true, true>(p, s_todo[i], smem4);
+        __syncthreads();  // (the next primitive restages the LDS this one's last readers may still be in)
+    }
+}
+
 }  // namespace mvp
 
-extern "C" int mvp_march_backward(int N, int H, int W, int K, const float *raypos, const float *raydir,
-                                  float stepsize, const float *tminmax, const float *nodeaabb,
-                                  const float *primpos, const float *primrot, const float *primscale, int TD,
-                                  int TH, int TW, const float *tplate, int WD, int WH, int WW, const float *warp,
-                                  const float *raysat, const uint32_t *rayaux, uint32_t *primlist_count,
-                                  const uint32_t *primlist, int primlist_cap, const float *grad_rayrgba,
-                                  float *grad_primpos, float *grad_primrot, float *grad_primscale,
-                                  float *grad_tplate, float *grad_warp, float fadescale, float fadeexp,
-                                  uint32_t *diag, void *stream) {
+// hslab: tplate points at fp16 RGBA slabs (mvp_march_backward_half: 8^3, no warp field)
+static int march_backward_impl(int N, int H, int W, int K, const float *raypos, const float *raydir, float stepsize,
+                               const float *tminmax, const float *nodeaabb, const float *primpos, const float *primrot,
+                               const float *primscale, int TD, int TH, int TW, const float *tplate, int WD, int WH, int WW,
+                               const float *warp, const float *raysat, const uint32_t *rayaux, uint32_t *primlist_count,
+                               const uint32_t *primlist, int primlist_cap, const float *grad_rayrgba, float *grad_primpos,
+                               float *grad_primrot, float *grad_primscale, float *grad_tplate, float *grad_warp,
+                               float fadescale, float fadeexp, uint32_t *diag, void *stream, bool hslab) {
     using namespace mvp;
     MarchParams p = {};
+    if (hslab && (warp || grad_warp)) return MVP_ERR_BADARG;
+    if (hslab && K > 0 && (TD != 8 || TH != 8 || TW != 8 || (unsigned long long)K * 4096ull >= (1ull << 32)))
+        return MVP_ERR_UNSUPPORTED;
     p.N = N, p.H = H, p.W = W, p.K = K, p.TD = TD, p.TH = TH, p.TW = TW;
     p.WD = WD, p.WH = WH, p.WW = WW, p.warp = warp, p.grad_warp = grad_warp;
     if (warp && (WD < 2 || WH < 2 || WW < 2)) return MVP_ERR_UNSUPPORTED;
@@ -1274,7 +1326,16 @@ extern "C" int mvp_march_backward(int N, int H, int W, int K, const float *raypo
         else                                                                                       \
             hipLaunchKernelGGL((bwd_prim_kernel<F8_, 0, 2, true>), grid, block, lds, st, p);       \
     }
-        if (warp && fade8)
+        if (hslab) {
+            if (pw == 3 && fade8)
+                hipLaunchKernelGGL((bwd_prim_hslab_kernel<true, 3>), grid, block, lds, st, p);
+            else if (pw == 3)
+                hipLaunchKernelGGL((bwd_prim_hslab_kernel<false, 3>), grid, block, lds, st, p);
+            else if (fade8)
+                hipLaunchKernelGGL((bwd_prim_hslab_kernel<true, 2>), grid, block, lds, st, p);
+            else
+                hipLaunchKernelGGL((bwd_prim_hslab_kernel<false, 2>), grid, block, lds, st, p);
+        } else if (warp && fade8)
             MVP_LAUNCH_PRIMW(true)
         else if (warp)
             MVP_LAUNCH_PRIMW(false)
@@ -1302,7 +1363,11 @@ extern "C" int mvp_march_backward(int N, int H, int W, int K, const float *raypo
                 lds2 += VW * 16 + VWp * 12;
             }
             const dim3 g2((unsigned)(pb < 2048 ? pb : 2048)), b2(kPreciseWaves * 64);
-            if (warp && fade8)
+            if (hslab && fade8)
+                hipLaunchKernelGGL((bwd_prim_precise_hslab_kernel<true>), g2, b2, lds2, st, p2, (int)pb);
+            else if (hslab)
+                hipLaunchKernelGGL((bwd_prim_precise_hslab_kernel<false>), g2, b2, lds2, st, p2, (int)pb);
+            else if (warp && fade8)
                 hipLaunchKernelGGL((bwd_prim_precise_kernel<true, true>), g2, b2, lds2, st, p2, (int)pb);
             else if (warp)
                 hipLaunchKernelGGL((bwd_prim_precise_kernel<false, true>), g2, b2, lds2, st, p2, (int)pb);
@@ -1319,7 +1384,12 @@ extern "C" int mvp_march_backward(int N, int H, int W, int K, const float *raypo
     int fb = p.total_packets;
     if (!p.fallback_all && fb > 256 * 16) fb = 256 * 16;  // persistent-style grid for the rarely-taken path
     const dim3 grid((unsigned)fb), block(kWave);
-    if (warp) {
+    if (hslab) {
+        if (fade8)
+            hipLaunchKernelGGL((march_hslab_kernel<true, true>), grid, block, 0, st, p);
+        else
+            hipLaunchKernelGGL((march_hslab_kernel<true, false>), grid, block, 0, st, p);
+    } else if (warp) {
         if (fade8)
             hipLaunchKernelGGL((march_kernel<true, true, true>), grid, block, 0, st, p);
         else
@@ -1331,4 +1401,35 @@ extern "C" int mvp_march_backward(int N, int H, int W, int K, const float *raypo
             hipLaunchKernelGGL((march_kernel<true, false, false>), grid, block, 0, st, p);
     }
     return launch_status();
+}
+
+extern "C" int mvp_march_backward(int N, int H, int W, int K, const float *raypos, const float *raydir,
+                                  float stepsize, const float *tminmax, const float *nodeaabb,
+                                  const float *primpos, const float *primrot, const float *primscale, int TD,
+                                  int TH, int TW, const float *tplate, int WD, int WH, int WW, const float *warp,
+                                  const float *raysat, const uint32_t *rayaux, uint32_t *primlist_count,
+                                  const uint32_t *primlist, int primlist_cap, const float *grad_rayrgba,
+                                  float *grad_primpos, float *grad_primrot, float *grad_primscale,
+                                  float *grad_tplate, float *grad_warp, float fadescale, float fadeexp,
+                                  uint32_t *diag, void *stream) {
+    return march_backward_impl(N, H, W, K, raypos, raydir, stepsize, tminmax, nodeaabb, primpos, primrot, primscale, TD, TH,
+                               TW, tplate, WD, WH, WW, warp, raysat, rayaux, primlist_count, primlist, primlist_cap,
+                               grad_rayrgba, grad_primpos, grad_primrot, grad_primscale, grad_tplate, grad_warp, fadescale,
+                               fadeexp, diag, stream, false);
+}
+
+// The backward over fp16 slabs (tplate_half [N,K,8,8,8,4] fp16, the slabs the forward marched): the same owners and hand-off
+// as mvp_march_backward; grad_tplate [N,K,8,8,8,4] stays FP32 and is overwritten.
+extern "C" int mvp_march_backward_half(int N, int H, int W, int K, const float *raypos, const float *raydir,
+                                       float stepsize, const float *tminmax, const float *nodeaabb,
+                                       const float *primpos, const float *primrot, const float *primscale, int TD,
+                                       int TH, int TW, const void *tplate_half, const float *raysat,
+                                       const uint32_t *rayaux, uint32_t *primlist_count, const uint32_t *primlist,
+                                       int primlist_cap, const float *grad_rayrgba, float *grad_primpos,
+                                       float *grad_primrot, float *grad_primscale, float *grad_tplate, float fadescale,
+                                       float fadeexp, uint32_t *diag, void *stream) {
+    return march_backward_impl(N, H, W, K, raypos, raydir, stepsize, tminmax, nodeaabb, primpos, primrot, primscale, TD, TH,
+                               TW, reinterpret_cast<const float *>(tplate_half), 0, 0, 0, nullptr, raysat, rayaux,
+                               primlist_count, primlist, primlist_cap, grad_rayrgba, grad_primpos, grad_primrot,
+                               grad_primscale, grad_tplate, nullptr, fadescale, fadeexp, diag, stream, true);
 }

@@ -528,6 +528,38 @@ __device__ __forceinline__ float4 sample_slab_h(const void *__restrict__ Timg, u
     return v;
 }
 
+// ---- half-precision slabs on the TRAINING path (halfslab.mvpraymarch_half) ------------------------------------------------
+// The forward with hand-off and both backward owners read the same fp16 slabs; the gradients are those of the march at the
+// ROUNDED values.  Widening fp16 -> fp32 is exact, so every sampler here is the fp32 sampler's arithmetic on widened corners:
+// the result is bit for bit what the fp32 path gives on template_half.float() (tests/test_gpu_half_train.py).
+typedef _Float16 hvox __attribute__((ext_vector_type(4), aligned(8)));  // one fp16 RGBA voxel
+__device__ __forceinline__ float4 widen_vox(const hvox h) { return make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w); }
+// voxel at FLOAT index `fidx` of the fp32 layout (4 floats per voxel), read from the fp16 slab block Th (8 bytes per voxel)
+__device__ __forceinline__ float4 load_vox_h(const char *__restrict__ Th, size_t fidx) {
+    return widen_vox(*reinterpret_cast<const hvox *>(Th + fidx * 2));
+}
+// sample_slab_c over fp16 slabs: sample_slab_h's four 16-byte gathers, the corners widened, then tri_interp exactly as the fp32
+// sampler (sample_slab_h's first product is an fma with +0, which may differ from the fp32 path in the sign of a zero)
+template <bool FADE8, int TS>
+__device__ __forceinline__ float4 sample_slab_hw(const void *__restrict__ Timg, uint32_t kbyte, f3 y, float fadescale,
+                                                 float fadeexp) {
+#pragma clang fp contract(off)
+    const float fade = fade_pinned<FADE8>(y, fadescale, fadeexp);
+    const TriF t = tri_setup_f<TS>(y);                       // (t.off counts 16-byte voxels: half of it here)
+    constexpr int bH = TS * 8, bD = TS * TS * 8;             // byte strides of the fp16 slab
+    const char *pc = reinterpret_cast<const char *>(Timg) + (size_t)(kbyte + (t.off >> 1));
+    const h8 p00 = *reinterpret_cast<const h8 *>(pc), p01 = *reinterpret_cast<const h8 *>(pc + bH);
+    const h8 p10 = *reinterpret_cast<const h8 *>(pc + bD), p11 = *reinterpret_cast<const h8 *>(pc + bD + bH);
+#define MVP_LO(P_) make_float4((float)P_[0], (float)P_[1], (float)P_[2], (float)P_[3])
+#define MVP_HI(P_) make_float4((float)P_[4], (float)P_[5], (float)P_[6], (float)P_[7])
+    float4 v = tri_interp(t, MVP_LO(p00), MVP_HI(p00), MVP_LO(p01), MVP_HI(p01), MVP_LO(p10), MVP_HI(p10), MVP_LO(p11),
+                          MVP_HI(p11));
+#undef MVP_LO
+#undef MVP_HI
+    v.w = v.w * fade;
+    return v;
+}
+
 // ---- warp-field path (algo 1: PrimSamplerTW<true>, primsampler.h:53-58,82-88) -------------------------------------
 // The warped coordinate y1 may leave (-1,1)^3, so the template lookup needs the reference's general form: normalised
 // coordinate clamped to +-100, floor, zero padding through per-corner bounds tests (utils.h:414-498).  This guarded form is

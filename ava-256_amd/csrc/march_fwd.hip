@@ -1,5 +1,6 @@
 // march_fwd.hip -- C-ABI entry points of the forward march (include/mvp_abi.h: mvp_march_forward,
-// mvp_march_forward_cams, mvp_march_render_half) and the instantiations of march_kernel<false, ..> they launch.
+// mvp_march_forward_cams, mvp_march_render_half, mvp_march_forward_half, mvp_march_forward_cams_half) and the
+// instantiations of march_kernel<false, ..> (march_half_kernel, march_hslab_kernel<false, ..>) they launch.
 //   /root/reference/extensions/mvpraymarch/mvpraymarch.cpp:38-66 (raymarch_forward_cuda), mvpraymarch_kernel.cu:35-120
 #include "march_packet.h"
 
@@ -15,9 +16,14 @@ static int march_forward_impl(int N, int H, int W, int K, const float *raypos, c
                               const float *tplate, int WD, int WH, int WW, const float *warp, float *rayrgba,
                               float *raysat, uint32_t *rayaux, uint32_t *primlist_count, uint32_t *primlist,
                               int primlist_cap, float fadescale, float fadeexp, uint32_t *diag, void *stream,
-                              bool half_slabs = false) {
+                              bool half_slabs = false, bool hslab_train = false) {
     using namespace mvp;
     MarchParams p = {};
+    if (hslab_train) {  // fp16 RGBA slabs with the hand-off to mvp_march_backward_half: 8^3 slabs, no warp field
+        if (warp) return MVP_ERR_BADARG;
+        if (K > 0 && (TD != 8 || TH != 8 || TW != 8 || (unsigned long long)K * 4096ull >= (1ull << 32)))
+            return MVP_ERR_UNSUPPORTED;
+    }
     if (half_slabs) {  // the opt-in render path over fp16 RGBA slabs: forward only, nothing handed to a backward, 8^3 slabs
         if (warp || raysat || rayaux || primlist_count || primlist) return MVP_ERR_BADARG;
         if (TD != 8 || TH != 8 || TW != 8 || (unsigned long long)K * 4096ull >= (1ull << 32)) return MVP_ERR_UNSUPPORTED;
@@ -78,6 +84,11 @@ static int march_forward_impl(int N, int H, int W, int K, const float *raypos, c
             hipLaunchKernelGGL((march_half_kernel<true>), grid, block, 0, st, p);
         else
             hipLaunchKernelGGL((march_half_kernel<false>), grid, block, 0, st, p);
+    } else if (hslab_train) {
+        if (fade8)
+            hipLaunchKernelGGL((march_hslab_kernel<false, true>), grid, block, 0, st, p);
+        else
+            hipLaunchKernelGGL((march_hslab_kernel<false, false>), grid, block, 0, st, p);
     } else {
         // the reference's slab size (and BASELINE's) gets compile-time strides and 32-bit slab offsets
         const bool cube8 = TD == 8 && TH == 8 && TW == 8 && (unsigned long long)K * 8192ull < (1ull << 32);
@@ -140,4 +151,34 @@ extern "C" int mvp_march_render_half(int N, int H, int W, int K, const float *ra
     return march_forward_impl(N, H, W, K, raypos, raydir, nullptr, stepsize, tminmax, nodeaabb, primpos, primrot, primscale,
                               TD, TH, TW, tp, 0, 0, 0, nullptr, rayrgba, nullptr, nullptr, nullptr, nullptr, 0, fadescale,
                               fadeexp, diag, stream, true);
+}
+
+// The training path over HALF-PRECISION slabs: mvp_march_forward / mvp_march_forward_cams without the warp field, reading fp16
+// RGBA slabs (8^3) and writing the full hand-off (raysat, rayaux, lists) for mvp_march_backward_half.  Bit for bit the fp32
+// forward on the widened slabs.
+extern "C" int mvp_march_forward_half(int N, int H, int W, int K, const float *raypos, const float *raydir,
+                                      float stepsize, const float *tminmax, const float *nodeaabb, const float *primpos,
+                                      const float *primrot, const float *primscale, int TD, int TH, int TW,
+                                      const void *tplate_half, float *rayrgba, float *raysat, uint32_t *rayaux,
+                                      uint32_t *primlist_count, uint32_t *primlist, int primlist_cap, float fadescale,
+                                      float fadeexp, uint32_t *diag, void *stream) {
+    return march_forward_impl(N, H, W, K, raypos, raydir, nullptr, stepsize, tminmax, nodeaabb, primpos, primrot,
+                              primscale, TD, TH, TW, reinterpret_cast<const float *>(tplate_half), 0, 0, 0, nullptr, rayrgba,
+                              raysat, rayaux, primlist_count, primlist, primlist_cap, fadescale, fadeexp, diag, stream,
+                              false, true);
+}
+
+extern "C" int mvp_march_forward_cams_half(int N, int H, int W, int K, const float *campos, const float *camrot,
+                                           const float *focal, const float *princpt, const float *pixelcoords,
+                                           float volradius, float stepsize, const float *nodeaabb, const float *primpos,
+                                           const float *primrot, const float *primscale, int TD, int TH, int TW,
+                                           const void *tplate_half, float *rayrgba, float *raysat, uint32_t *rayaux,
+                                           uint32_t *primlist_count, uint32_t *primlist, int primlist_cap,
+                                           float *raypos_out, float *raydir_out, float *tminmax_out, float fadescale,
+                                           float fadeexp, uint32_t *diag, void *stream) {
+    const CameraArgs cams = {campos, camrot, focal, princpt, pixelcoords, volradius, raypos_out, raydir_out, tminmax_out};
+    return march_forward_impl(N, H, W, K, nullptr, nullptr, &cams, stepsize, nullptr, nodeaabb, primpos, primrot,
+                              primscale, TD, TH, TW, reinterpret_cast<const float *>(tplate_half), 0, 0, 0, nullptr, rayrgba,
+                              raysat, rayaux, primlist_count, primlist, primlist_cap, fadescale, fadeexp, diag, stream,
+                              false, true);
 }

@@ -11,8 +11,10 @@ namespace mvp {
 // profiles/r04_fwd_ab_quad.txt, profiles/r05_timing_variants.patch.)
 __device__ __forceinline__ void packet_sync() { __syncthreads(); }
 
-// HALF (forward, TS > 0, no warp field, no hand-off): p.tplate points at fp16 RGBA slabs (sample_slab_h)
-template <bool BWD, bool FADE8, bool WARP, int TS, bool HALF = false>
+// HSLAB (TS > 0, no warp field): p.tplate points at fp16 RGBA slabs, 8 bytes per voxel.  The forward samples them with
+// sample_slab_hw (with RENDER: sample_slab_h), the ray-centric backward widens its corners (load_vox_h).
+// RENDER (forward, HSLAB): the render path -- no hand-off to a backward: no list records, no raysat / rayaux, no NaN tracking.
+template <bool BWD, bool FADE8, bool WARP, int TS, bool HSLAB = false, bool RENDER = false>
 __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, int *s_a, int *s_b, float4 *s_rec,
                                              uint32_t *s_tab, const bool emit_all) {
     constexpr bool FAST = !BWD;  // the lane-independent sweep exists for the forward only (round 6: the warp-field one too)
@@ -319,7 +321,7 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
             if (!some) lo = 0x7fffffff, hi = -1;
             const unsigned long long somem = __ballot(some);
             if (somem != 0ull) {  // wave-uniform
-                if constexpr (HALF) {
+                if constexpr (RENDER) {
                     // render path: no list is handed to a backward, so the packet's step range (two wave reductions per listed
                     // primitive) is not needed -- only the test that every step index fits the crossing table's field
                     if (nh >= kFastSlots || __ballot(some && hi > kFastMaxStep) != 0ull) {
@@ -464,7 +466,7 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
         }
         const size_t V4 = (size_t)p.TD * p.TH * p.TW * 4;
         const float *T = p.tplate + (size_t)n * K * V4;
-        // (HALF: the same pointer addresses fp16 RGBA slabs, 8 bytes per voxel)
+        // (HSLAB: the same pointer addresses fp16 RGBA slabs, 8 bytes per voxel)
         const char *Th = reinterpret_cast<const char *>(p.tplate) + (size_t)n * K * (V4 * 2);
         float *gT = BWD ? p.grad_tplate + (size_t)n * K * V4 : nullptr;
         const int sW = 4, sH = p.TW * 4, sD = p.TH * p.TW * 4;  // float strides of the channels-last slab
@@ -532,16 +534,19 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
                                 v = sample_warped<FADE8>(p.warp + ((size_t)n * K + k) * ((size_t)p.WD * p.WH * p.WW * 3),
                                                          T + (size_t)k * V4, y, p.WD, p.WH, p.WW, p.TD, p.TH, p.TW,
                                                          p.fadescale, p.fadeexp);
-                            else if constexpr (HALF)
+                            else if constexpr (RENDER)
                                 v = sample_slab_h<FADE8, TS>(Th, (uint32_t)k * (uint32_t)(TS * TS * TS * 8), y, p.fadescale,
                                                              p.fadeexp);
+                            else if constexpr (HSLAB)
+                                v = sample_slab_hw<FADE8, TS>(Th, (uint32_t)k * (uint32_t)(TS * TS * TS * 8), y, p.fadescale,
+                                                              p.fadeexp);
                             else if constexpr (TS > 0)
                                 v = sample_slab_c<FADE8, TS>(T, (uint32_t)k * (uint32_t)(TS * TS * TS * 16), y, p.fadescale,
                                                              p.fadeexp);
                             else
                                 v = sample_slab<FADE8>(T + (size_t)k * V4, y, p.TD, p.TH, p.TW, p.fadescale, p.fadeexp);
                             float contrib;
-                            if constexpr (!HALF) nanw = nanw || (v.w != v.w);   // (only the hand-off to a backward reads it)
+                            if constexpr (!RENDER) nanw = nanw || (v.w != v.w);   // (only the hand-off to a backward reads it)
                             if (composite(rgba, v, dt, contrib)) {  // saturated: nothing after this sample is evaluated
                                 raysat = mk3(v.x, v.y, v.z);
                                 satkey = ((uint32_t)s << 9) | (uint32_t)slot;
@@ -629,9 +634,12 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
                                     v = sample_warped<FADE8>(p.warp + ((size_t)n * K + k) * VW3, T + (size_t)k * V4, y, p.WD,
                                                              p.WH, p.WW, p.TD, p.TH, p.TW, p.fadescale, p.fadeexp);
                                 } else {
-                                    if constexpr (HALF)
+                                    if constexpr (RENDER)
                                         v = sample_slab_h<FADE8, TS>(Th, (uint32_t)k * (uint32_t)(TS * TS * TS * 8), y,
                                                                      p.fadescale, p.fadeexp);
+                                    else if constexpr (HSLAB)
+                                        v = sample_slab_hw<FADE8, TS>(Th, (uint32_t)k * (uint32_t)(TS * TS * TS * 8), y,
+                                                                      p.fadescale, p.fadeexp);
                                     else if constexpr (TS > 0)
                                         v = sample_slab_c<FADE8, TS>(T, (uint32_t)k * (uint32_t)(TS * TS * TS * 16), y,
                                                                      p.fadescale, p.fadeexp);
@@ -777,15 +785,23 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
                             const float wy1 = iy - (float)y0, wy0 = (float)(y0 + 1) - iy;
                             const float wz1 = iz - (float)z0, wz0 = (float)(z0 + 1) - iz;
                             const size_t vbase = (size_t)k * V4 + (size_t)z0 * sD + (size_t)y0 * sH + (size_t)x0 * sW;
-                            const float *Tp = T + vbase;
-                            const float4 c000 = *reinterpret_cast<const float4 *>(Tp);
-                            const float4 c001 = *reinterpret_cast<const float4 *>(Tp + sW);
-                            const float4 c010 = *reinterpret_cast<const float4 *>(Tp + sH);
-                            const float4 c011 = *reinterpret_cast<const float4 *>(Tp + sH + sW);
-                            const float4 c100 = *reinterpret_cast<const float4 *>(Tp + sD);
-                            const float4 c101 = *reinterpret_cast<const float4 *>(Tp + sD + sW);
-                            const float4 c110 = *reinterpret_cast<const float4 *>(Tp + sD + sH);
-                            const float4 c111 = *reinterpret_cast<const float4 *>(Tp + sD + sH + sW);
+                            float4 c000, c001, c010, c011, c100, c101, c110, c111;
+                            if constexpr (HSLAB) {  // fp16 slab: the same corners, widened (exact)
+                                c000 = load_vox_h(Th, vbase), c001 = load_vox_h(Th, vbase + sW);
+                                c010 = load_vox_h(Th, vbase + sH), c011 = load_vox_h(Th, vbase + sH + sW);
+                                c100 = load_vox_h(Th, vbase + sD), c101 = load_vox_h(Th, vbase + sD + sW);
+                                c110 = load_vox_h(Th, vbase + sD + sH), c111 = load_vox_h(Th, vbase + sD + sH + sW);
+                            } else {
+                                const float *Tp = T + vbase;
+                                c000 = *reinterpret_cast<const float4 *>(Tp);
+                                c001 = *reinterpret_cast<const float4 *>(Tp + sW);
+                                c010 = *reinterpret_cast<const float4 *>(Tp + sH);
+                                c011 = *reinterpret_cast<const float4 *>(Tp + sH + sW);
+                                c100 = *reinterpret_cast<const float4 *>(Tp + sD);
+                                c101 = *reinterpret_cast<const float4 *>(Tp + sD + sW);
+                                c110 = *reinterpret_cast<const float4 *>(Tp + sD + sH);
+                                c111 = *reinterpret_cast<const float4 *>(Tp + sD + sH + sW);
+                            }
                             const float w000 = wx0 * wy0 * wz0, w001 = wx1 * wy0 * wz0, w010 = wx0 * wy1 * wz0,
                                         w011 = wx1 * wy1 * wz0, w100 = wx0 * wy0 * wz1, w101 = wx1 * wy0 * wz1,
                                         w110 = wx0 * wy1 * wz1, w111 = wx1 * wy1 * wz1;
@@ -920,7 +936,7 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
     // one 64-bit LDS atomic per dead crossing, nothing at all in packets without a saturated ray), and a record whose mask is
     // empty is not appended: the backward's phase 1 neither loads it nor examines its rays.  The entries themselves are where the
     // exact test left them: (ent0, rg0, msk0) in registers, s_b / s_a (which the slot-synchronous sweep only reads) otherwise.
-    if (!BWD && !HALF && p.pl_count != nullptr && nh > 0) {
+    if (!BWD && !RENDER && p.pl_count != nullptr && nh > 0) {
         uint32_t *flags = p.pl_count + (size_t)p.N * K;
         if (FAST && fast) {
             const bool satd = satkey != kNoSat;
@@ -970,7 +986,7 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
         }
     }
 
-    if (!BWD && !HALF && p.pl_count != nullptr) {
+    if (!BWD && !RENDER && p.pl_count != nullptr) {
         // max |raysat| over the packet -> tail word [2] (the backward's fixed-point bound).  |-1| = 1 when unsaturated:
         // the host pre-sets the word to 1.0f, and only a packet that can raise it touches it.  (One same-address
         // atomic per packet -- 327 680 of them at C2 -- serialised in L2 and cost 2.5 ms of a 9.4 ms kernel.)
@@ -986,7 +1002,7 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
     }
     if (!BWD && inimg) {
         reinterpret_cast<float4 *>(p.rayrgba)[r] = rgba;  // primaccum.h:51-56
-        if constexpr (HALF) return;   // (render path: nothing is handed to a backward)
+        if constexpr (RENDER) return;   // (render path: nothing is handed to a backward)
         if (p.raysat) {
             float *sp = p.raysat + r * 3;
             MVP_STREAM_STOREF(sp, raysat.x), MVP_STREAM_STOREF(sp + 1, raysat.y), MVP_STREAM_STOREF(sp + 2, raysat.z);
@@ -1041,7 +1057,35 @@ __global__ __launch_bounds__(kWave) void march_half_kernel(const MarchParams p) 
     int *s_a = reinterpret_cast<int *>(smem + kRecSlots * 16);
     int *s_b = s_a + kMaxList;
     uint32_t *s_tab = smem + kFastSlots * 16;
-    march_packet<false, FADE8, false, 8, true>(p, blockIdx.x, s_a, s_b, s_rec, s_tab, true);
+    march_packet<false, FADE8, false, 8, true, true>(p, blockIdx.x, s_a, s_b, s_rec, s_tab, true);
+}
+
+// The training path over fp16 slabs (8^3 only): the forward WITH hand-off (BWD = false) and the ray-centric backward
+// (BWD = true), the same bodies as march_kernel's with the slab read through sample_slab_hw / load_vox_h.
+template <bool BWD, bool FADE8>
+__global__ __launch_bounds__(kWave) void march_hslab_kernel(const MarchParams p) {
+    constexpr int kSlowWords = kRecSlots * 16 + 2 * kMaxList;
+    constexpr int kFastWords = kFastSlots * 16 + kFastCross * kWave;
+    constexpr int kWords = (!BWD && kFastWords > kSlowWords) ? kFastWords : kSlowWords;
+    __shared__ __attribute__((aligned(16))) uint32_t smem[kWords];
+    float4 *s_rec = reinterpret_cast<float4 *>(smem);
+    int *s_a = reinterpret_cast<int *>(smem + kRecSlots * 16);
+    int *s_b = s_a + kMaxList;
+    uint32_t *s_tab = smem + kFastSlots * 16;
+    if (BWD) {
+        bool emit_all = p.fallback_all != 0;
+        if (!emit_all) {
+            const uint32_t flags = p.pl_count[(size_t)p.N * p.K] & ~kFlagBwdPrecise;
+            if (flags == 0u) return;
+            emit_all = (flags & kFlagGlobal) != 0u;
+        }
+        for (int b = blockIdx.x; b < p.total_packets; b += gridDim.x) {
+            march_packet<BWD, FADE8, false, 8, true>(p, b, s_a, s_b, s_rec, s_tab, emit_all);
+            __syncthreads();
+        }
+    } else {
+        march_packet<BWD, FADE8, false, 8, true>(p, blockIdx.x, s_a, s_b, s_rec, s_tab, true);
+    }
 }
 
 }  // namespace mvp

@@ -9,15 +9,34 @@ sweep is bound by its gathers, so a caller that RENDERS (no gradients) may hand 
     rgba = render_half_from_cameras(campos, camrot, focal, princpt, pixelcoords, volradius, stepsize, primtransf, th)
 
 Same sample set, weights, interpolation and compositing in fp32; only the slab VALUES carry the fp16 storage rounding
-(2^-11 relative).  Never the training path and never the headline number: `mvpraymarch(...)` keeps fp32 slabs, and these
-functions refuse to run with gradients enabled on their inputs.  8^3 slabs (the reference's size)."""
+(2^-11 relative).  Never the headline number: `mvpraymarch(...)` keeps fp32 slabs, and these render functions refuse to run
+with gradients enabled on their inputs.  8^3 slabs (the reference's size).
+
+TRAINING over fp16 slabs is a separate, differentiable operator (opt-in; trainloop.RaymarchTrainModel(half_slabs=True)):
+
+    rgba = mvpraymarch_half(raypos, raydir, stepsize, tminmax, (primpos, primrot, primscale), template, template_half=None)
+    rgba = mvpraymarch_half_from_cameras(campos, camrot, focal, princpt, pixelcoords, volradius, stepsize, primtransf,
+                                         template, template_half=None)
+
+The fp16 rounding is a straight-through step: the rays march over template_half (the round-to-nearest-even copy of the fp32
+`template`; made here with template_to_half when not given), and the gradients -- fp32, for template and the three pose
+tensors -- are the march's gradients at the rounded slab values.  The differentiable slab input is the fp32 master: autograd
+casts a gradient to its input's dtype, and fp16 slab gradients would underflow.  Bit for bit what mvpraymarch gives on
+template_half.float() (tests/test_gpu_half_train.py).  No warp field, 8^3 slabs."""
+import importlib
 import math
 
 import torch
 
+from torch.autograd import Function
+
 from . import _hooks, _lib
 from ._tensors import aligned, ptr, require_device_f32, stream_ptr
 from .mvpraymarch import build_accel
+
+# the MODULE (the package re-exports a function of that name): alloc_handoff is looked up on it at call time, so that
+# _hooks.patched_handoff applies to this operator too
+_mvp = importlib.import_module(__package__ + ".mvpraymarch")
 
 
 def template_to_half(template):
@@ -146,3 +165,237 @@ def render_half_from_cameras(campos, camrot, focal, princpt, pixelcoords, volrad
                 ptr(th), ptr(rayrgba), float(fadescale), float(fadeexp), ptr(_hooks.diag), stream_ptr(dev)),
                 "mvp_march_render_half")
     return rayrgba
+
+
+# ---- training over fp16 slabs ------------------------------------------------------------------------------------------
+
+def assemble_template_frames_half(tex, opacity, gain, nboxes, boxsize=8):
+    """The fp16 twin of assemble.assemble_template_frames, without gradients: tex [1,3*B,nh*B,nh*B], opacity [1,B,nh*B,nh*B],
+    gain [F] -> [F,nboxes,B,B,B,4] float16 = (gain[f] * assemble(tex, opacity)) rounded to nearest even -- bit for bit
+    assemble_template_frames(...).half(), without the fp32 slabs ever being read back."""
+    tex = require_device_f32("tex", tex)
+    opacity = require_device_f32("opacity", opacity)
+    gain = require_device_f32("gain", gain)
+    nh = int(math.isqrt(nboxes))
+    if nh * nh != nboxes:
+        raise ValueError("nboxes must be a square (rgb.py:130-131)")
+    S, F = nh * boxsize, gain.numel()
+    if tex.shape != (1, 3 * boxsize, S, S) or opacity.shape != (1, boxsize, S, S) or gain.dim() != 1:
+        raise ValueError("tex / opacity / gain must be [1,%d,%d,%d] / [1,%d,%d,%d] / [F]" % (3 * boxsize, S, S, boxsize, S, S))
+    _same_device(tex, opacity, gain)
+    dev = tex.device
+    with torch.no_grad():
+        out = torch.empty((F, nboxes, boxsize, boxsize, boxsize, 4), device=dev, dtype=torch.float16)
+        with torch.cuda.device(dev), _hooks.timed("assemble_frames_half", dev):
+            _lib.check(_lib.get_lib().mvp_template_assemble_frames_forward_half(
+                F, nh, boxsize, ptr(tex), ptr(opacity), ptr(gain), ptr(out), stream_ptr(dev)),
+                "mvp_template_assemble_frames_forward_half")
+    return out
+
+
+def _check_train_half_args(N, primpos, primrot, primscale, template, template_half, warp, algo, others):
+    """Everything the training operator refuses, decided from shapes, dtypes and devices alone (no device work)."""
+    if warp is not None or algo != 0:
+        raise NotImplementedError("mvpraymarch_half has no warp-field sampler (algo 0 only)")
+    for name, t in (("primpos", primpos), ("primrot", primrot), ("primscale", primscale), ("template", template)):
+        if not torch.is_tensor(t):
+            raise TypeError("%s must be a tensor" % name)
+    if template.dtype != torch.float32:
+        raise RuntimeError("template must be the float32 master (its gradient is returned in its dtype), got %s; pass the "
+                           "fp16 copy as template_half" % template.dtype)
+    K = primpos.size(1) if primpos.dim() == 3 else -1
+    if primpos.shape != (N, K, 3) or primrot.shape != (N, K, 3, 3) or primscale.shape != (N, K, 3):
+        raise ValueError("primpos / primrot / primscale must be [N,K,3] / [N,K,3,3] / [N,K,3] with N = %d images" % N)
+    if template.dim() != 6 or template.size(-1) != 4 or tuple(template.shape[:2]) != (N, K):
+        raise ValueError("template must be [N,K,TD,TH,TW,4] with N = %d, K = %d, got %s" % (N, K, tuple(template.shape)))
+    if tuple(template.shape[2:5]) != (8, 8, 8):
+        raise NotImplementedError("the half-precision slab path takes 8^3 slabs, got %s" % (tuple(template.shape[2:5]),))
+    if template_half is not None:
+        if not torch.is_tensor(template_half) or template_half.dtype != torch.float16:
+            raise RuntimeError("template_half must be a float16 tensor (template_to_half / assemble_template_frames_half)")
+        if template_half.shape != template.shape:
+            raise ValueError("template_half %s must have the shape of template %s" % (tuple(template_half.shape),
+                                                                                     tuple(template.shape)))
+    _same_device(primpos, primrot, primscale, template, template_half, *others)
+    return K
+
+
+def _half_of(template, template_half):
+    """The slabs the march reads: the given rounding (not differentiable), or the one made here."""
+    if template_half is None:
+        return template_to_half(template)
+    if not template_half.is_cuda:
+        raise RuntimeError("template_half must be a CUDA/HIP tensor (there is no CPU path)")
+    if not template_half.is_contiguous():
+        raise RuntimeError("template_half must be contiguous")
+    return aligned(template_half.detach())
+
+
+def _forward_half_impl(ctx, rays, cams, stepsize, primpos, primrot, primscale, template, template_half, gradmode,
+                       fadescale, fadeexp):
+    """mvpraymarch._forward_impl over fp16 slabs: the same hand-off allocation (mvpraymarch.alloc_handoff, looked up at call
+    time so that _hooks.patched_handoff applies), list-capacity feedback and test hooks."""
+    fadescale, fadeexp = float(fadescale), float(fadeexp)
+    primpos = require_device_f32("primpos", primpos)
+    primrot = require_device_f32("primrot", primrot)
+    primscale = require_device_f32("primscale", primscale)
+    template = require_device_f32("template", template)
+    if cams is None:
+        raypos, raydir, tminmax = (aligned(require_device_f32(n, t)) for n, t in zip(("raypos", "raydir", "tminmax"), rays))
+        N, H, W = raypos.size(0), raypos.size(1), raypos.size(2)
+    else:
+        campos, camrot, focal, princpt, pc, W, H, volradius = cams
+        N = campos.size(0)
+        raypos = raydir = tminmax = None
+    K = primpos.size(1)
+    th = _half_of(template, template_half)
+    dev = primpos.device
+    _, _, nodeaabb = build_accel((primpos, primrot, primscale), 0, fixedorder=True)
+
+    rayrgba = torch.empty((N, H, W, 4), device=dev, dtype=torch.float32)
+    raysat = rayaux = pl_count = pl_list = None
+    pl_cap = 0
+    if gradmode:
+        raysat = torch.empty((N, H, W, 3), device=dev, dtype=torch.float32)
+        rayaux, pl_count, pl_list, pl_cap = _mvp.alloc_handoff(N, H, W, K, dev)
+    lib = _lib.get_lib()
+    with torch.cuda.device(dev), _hooks.timed("march_forward_half", dev):
+        if cams is None:
+            _lib.check(lib.mvp_march_forward_half(
+                N, H, W, K, ptr(raypos), ptr(raydir), float(stepsize), ptr(tminmax), ptr(nodeaabb), ptr(primpos),
+                ptr(primrot), ptr(primscale), 8, 8, 8, ptr(th), ptr(rayrgba), ptr(raysat), ptr(rayaux), ptr(pl_count),
+                ptr(pl_list), pl_cap, fadescale, fadeexp, ptr(_hooks.diag), stream_ptr(dev)), "mvp_march_forward_half")
+        else:
+            if gradmode:  # the backward's ray tensors, written by the forward march itself
+                raypos = torch.empty((N, H, W, 3), device=dev, dtype=torch.float32)
+                raydir = torch.empty((N, H, W, 3), device=dev, dtype=torch.float32)
+                tminmax = torch.empty((N, H, W, 2), device=dev, dtype=torch.float32)
+            _lib.check(lib.mvp_march_forward_cams_half(
+                N, H, W, K, ptr(campos), ptr(camrot), ptr(focal), ptr(princpt), ptr(pc), float(volradius),
+                float(stepsize), ptr(nodeaabb), ptr(primpos), ptr(primrot), ptr(primscale), 8, 8, 8, ptr(th),
+                ptr(rayrgba), ptr(raysat), ptr(rayaux), ptr(pl_count), ptr(pl_list), pl_cap, ptr(raypos), ptr(raydir),
+                ptr(tminmax), fadescale, fadeexp, ptr(_hooks.diag), stream_ptr(dev)), "mvp_march_forward_cams_half")
+
+    if pl_count is not None:
+        with torch.cuda.device(dev):
+            _mvp.note_list_demand(pl_count, N, H, W, K)
+    if _hooks.keep_raysat:
+        _hooks.last_raysat = raysat
+        _hooks.last_pl_count = pl_count
+        _hooks.last_flags_index = N * K
+        _hooks.last_handoff_shape = (N, H, W, K, pl_cap)
+    ctx.save_for_backward(raypos, raydir, tminmax, nodeaabb, primpos, primrot, primscale, th, raysat, rayaux, pl_count,
+                          pl_list)
+    ctx.pl_cap, ctx.stepsize, ctx.fade = pl_cap, float(stepsize), (fadescale, fadeexp)
+    return rayrgba
+
+
+def _backward_half_impl(ctx, grad_rayrgba):
+    (raypos, raydir, tminmax, nodeaabb, primpos, primrot, primscale, th, raysat, rayaux, pl_count,
+     pl_list) = ctx.saved_tensors
+    if raysat is None:
+        raise RuntimeError("backward through mvpraymarch_half needs grad mode enabled during the forward call")
+    N, H, W = raypos.size(0), raypos.size(1), raypos.size(2)
+    K = primpos.size(1)
+    dev = raypos.device
+    grad_rayrgba = aligned(grad_rayrgba.contiguous().float())
+    # all four are overwritten by the library; the slab gradient is fp32, shaped like the fp32 master
+    grad_primpos = torch.empty_like(primpos)
+    grad_primrot = torch.empty_like(primrot)
+    grad_primscale = torch.empty_like(primscale)
+    grad_template = torch.empty(th.shape, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev), _hooks.timed("march_backward_half", dev):
+        _lib.check(_lib.get_lib().mvp_march_backward_half(
+            N, H, W, K, ptr(raypos), ptr(raydir), ctx.stepsize, ptr(tminmax), ptr(nodeaabb), ptr(primpos), ptr(primrot),
+            ptr(primscale), 8, 8, 8, ptr(th), ptr(raysat), ptr(rayaux), ptr(pl_count), ptr(pl_list), ctx.pl_cap,
+            ptr(grad_rayrgba), ptr(grad_primpos), ptr(grad_primrot), ptr(grad_primscale), ptr(grad_template),
+            ctx.fade[0], ctx.fade[1], ptr(_hooks.diag), stream_ptr(dev)), "mvp_march_backward_half")
+    return grad_primpos, grad_primrot, grad_primscale, grad_template
+
+
+class MVPRaymarchHalf(Function):
+    """MVPRaymarch over fp16 slabs (straight-through rounding; see the module docstring)."""
+
+    @staticmethod
+    def forward(ctx, raypos, raydir, stepsize, tminmax, primpos, primrot, primscale, template, template_half, gradmode,
+                fadescale, fadeexp):
+        return _forward_half_impl(ctx, (raypos, raydir, tminmax), None, stepsize, primpos, primrot, primscale, template,
+                                  template_half, gradmode, fadescale, fadeexp)
+
+    @staticmethod
+    def backward(ctx, grad_rayrgba):
+        gp, gr, gs, gt = _backward_half_impl(ctx, grad_rayrgba)
+        return None, None, None, None, gp, gr, gs, gt, None, None, None, None
+
+
+class MVPRaymarchHalfFromCameras(Function):
+    """MVPRaymarchFromCameras over fp16 slabs: rays made inside the march, written for the backward in grad mode."""
+
+    @staticmethod
+    def forward(ctx, campos, camrot, focal, princpt, pixelcoords, volradius, stepsize, primpos, primrot, primscale, template,
+                template_half, gradmode, fadescale, fadeexp, wh):
+        W, H = wh
+        cams = (campos, camrot, focal, princpt, pixelcoords, W, H, volradius)
+        return _forward_half_impl(ctx, None, cams, stepsize, primpos, primrot, primscale, template, template_half, gradmode,
+                                  fadescale, fadeexp)
+
+    @staticmethod
+    def backward(ctx, grad_rayrgba):
+        gp, gr, gs, gt = _backward_half_impl(ctx, grad_rayrgba)
+        return (None,) * 7 + (gp, gr, gs, gt) + (None,) * 5
+
+
+def mvpraymarch_half(raypos, raydir, stepsize, tminmax, primtransf, template, template_half=None, fadescale=8.0,
+                     fadeexp=8.0, warp=None, algo=0):
+    """mvpraymarch(...) over fp16 slabs, with gradients: template is the fp32 master [N,K,8,8,8,4]; template_half its
+    round-to-nearest-even copy (float16, same shape; made here when None).  Returns rayrgba [N,H,W,4] float32.  `warp` /
+    `algo` exist only to be refused (no warp-field sampler on this path)."""
+    primpos, primrot, primscale = _split_prims(primtransf)
+    for name, t in (("raypos", raypos), ("raydir", raydir), ("tminmax", tminmax)):
+        if not torch.is_tensor(t):
+            raise TypeError("%s must be a tensor" % name)
+    if raypos.dim() != 4 or raypos.size(3) != 3 or raydir.shape != raypos.shape or \
+            tminmax.shape != raypos.shape[:3] + (2,):
+        raise ValueError("raypos / raydir / tminmax must be [N,H,W,3] / [N,H,W,3] / [N,H,W,2]")
+    _check_train_half_args(raypos.size(0), primpos, primrot, primscale, template, template_half, warp, algo,
+                           (raypos, raydir, tminmax))
+    return MVPRaymarchHalf.apply(raypos, raydir, stepsize, tminmax, primpos, primrot, primscale, template, template_half,
+                                 torch.is_grad_enabled(), fadescale, fadeexp)
+
+
+def mvpraymarch_half_from_cameras(campos, camrot, focal, princpt, pixelcoords, volradius, stepsize, primtransf, template,
+                                  template_half=None, fadescale=8.0, fadeexp=8.0, warp=None, algo=0):
+    """mvpraymarch_from_cameras(...) over fp16 slabs, with gradients (see mvpraymarch_half).  pixelcoords: [N,H,W,2] tensor
+    or a (W, H) tuple."""
+    primpos, primrot, primscale = _split_prims(primtransf)
+    for name, t in (("campos", campos), ("camrot", camrot), ("focal", focal), ("princpt", princpt)):
+        if not torch.is_tensor(t):
+            raise TypeError("%s must be a tensor" % name)
+    N = campos.size(0)
+    if campos.shape != (N, 3) or camrot.shape != (N, 3, 3) or focal.shape != (N, 2) or princpt.shape != (N, 2):
+        raise ValueError("campos / camrot / focal / princpt must be [N,3] / [N,3,3] / [N,2] / [N,2]")
+    if isinstance(pixelcoords, tuple):
+        W, H = pixelcoords
+        pc = None
+    else:
+        if not torch.is_tensor(pixelcoords) or pixelcoords.dim() != 4 or pixelcoords.size(0) != N or \
+                pixelcoords.size(3) != 2:
+            raise ValueError("pixelcoords must be [N,H,W,2] or a (W, H) tuple")
+        H, W = pixelcoords.size(1), pixelcoords.size(2)
+        pc = pixelcoords
+    _check_train_half_args(N, primpos, primrot, primscale, template, template_half, warp, algo,
+                           (campos, camrot, focal, princpt, pc))
+    campos, camrot = require_device_f32("campos", campos), require_device_f32("camrot", camrot)
+    focal, princpt = require_device_f32("focal", focal), require_device_f32("princpt", princpt)
+    if pc is not None:
+        pc = aligned(require_device_f32("pixelcoords", pc))
+    return MVPRaymarchHalfFromCameras.apply(campos, camrot, focal, princpt, pc, float(volradius), stepsize, primpos,
+                                            primrot, primscale, template, template_half, torch.is_grad_enabled(),
+                                            fadescale, fadeexp, (int(W), int(H)))
+
+
+def _split_prims(primtransf):
+    if isinstance(primtransf, tuple):
+        return primtransf
+    return (primtransf[:, :, 0, :].contiguous(), primtransf[:, :, 1:4, :].contiguous(),
+            primtransf[:, :, 4, :].contiguous())

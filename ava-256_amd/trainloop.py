@@ -202,6 +202,9 @@ class SlabDecoderStandIn(nn.Module):
         # row N2; on CPU by the reference's own view / permute / relu / cat statements); a per-frame gain stands for the
         # view / expression conditioning.  Other K: per-primitive slab parameters and a per-primitive gain, eager.
         self.conv_layout = nh * nh == K
+        # set by RaymarchTrainModel(half_slabs=True): the frames form also emits `template_half`, the fp16 shadow of the
+        # slabs made straight from the decoder outputs (halfslab.assemble_template_frames_half; no fp32 read-back)
+        self.half_shadow = False
         if self.conv_layout:
             S = nh * slab
             self.tex = nn.Parameter(torch.randn(1, 3 * slab, S, S, generator=g))          # pre-activation, random-init statistics
@@ -273,12 +276,17 @@ class SlabDecoderStandIn(nn.Module):
         sch = schedule or {}
         rw = min(max(float(sch.get("residuals_weight", 1.0)), 0.0), 1.0)     # assembler.py:241
         gain = 1.0 + 0.1 * torch.tanh(self.gain(code))                      # [B,1] or [B,K]
+        template_half = None
         if self.conv_layout:
             if self.tex.is_cuda and self.tex.dtype == torch.float32:
                 # one pass each way: slabs made and scaled per frame in the hand-off kernel; its backward reads the
                 # incoming gradient once (it was: assemble + broadcast multiply, two gemv + the assemble backward)
                 from .assemble import assemble_template_frames
                 template = assemble_template_frames(self.tex, self.opacity, gain[:, 0].contiguous(), self.K, self.slab)
+                if self.half_shadow:
+                    from .halfslab import assemble_template_frames_half
+                    template_half = assemble_template_frames_half(self.tex.detach(), self.opacity.detach(),
+                                                                  gain[:, 0].detach().contiguous(), self.K, self.slab)
             else:
                 base = assemble_template_eager(self.tex, self.opacity, self.K, self.slab)
                 template = _FrameGain.apply(base[0], gain[:, 0])                            # [B,K,s,s,s,4]
@@ -294,6 +302,8 @@ class SlabDecoderStandIn(nn.Module):
         if rw < 1.0 and not fused_pose:                                       # assembler.py:242-245
             pos_res, rot_res, scale_res = pos_res * rw, rot_res * rw, scale_res * rw + (1.0 - rw)
         out = {}
+        if template_half is not None:
+            out["template_half"] = template_half
         if self.geometry:
             geo = _WideLinear.apply(code, self.geo_head.weight, self.geo_head.bias).view(B, self.K, 3) * self.vertstd \
                 + self.vertmean                                                              # assembler.py:100-103
@@ -450,8 +460,13 @@ class RaymarchTrainModel(nn.Module):
     def __init__(self, decoder: nn.Module, volradius: float = 256.0, dt: float = 1.0,
                  renderer: Optional[Callable] = None, colorcal: Optional[nn.Module] = None,
                  bgmodel: Optional[nn.Module] = None, encoder: Optional[nn.Module] = None, fused_rays: bool = True,
-                 fused_tail: bool = True):
+                 fused_tail: bool = True, half_slabs: bool = False):
+        """`half_slabs=True` (opt-in): the fused GPU branch marches fp16 copies of the decoder's slabs
+        (halfslab.mvpraymarch_half_from_cameras: fp16 forward, straight-through fp32 gradients to the fp32 template)."""
         super().__init__()
+        self.half_slabs = bool(half_slabs)
+        if self.half_slabs and hasattr(decoder, "half_shadow"):
+            decoder.half_shadow = True
         self.fused_rays = fused_rays  # rays made inside the forward march (SURVEY 8f row N1) instead of the two statements
         self.fused_tail = fused_tail  # colour calibration + matting + L1 sum as one kernel each way (csrc/pixeltail.hip)
         self.decoder = decoder
@@ -479,8 +494,18 @@ class RaymarchTrainModel(nn.Module):
             from .mvpraymarch import mvpraymarch_from_cameras
             from .pixeltail import decode_tail
             rm = self.raymarcher
-            rayrgba = mvpraymarch_from_cameras(campos, camrot, focal, princpt, pixelcoords, rm.volume_radius, rm.dt,
-                                               (decout["primpos"], decout["primrot"], decout["primscale"]), decout["template"])
+            prims = (decout["primpos"], decout["primrot"], decout["primscale"])
+            if self.half_slabs:
+                # fp16 slabs for the march: the decoder's own shadow (frames form), else the rounding of its fp32 slabs
+                from .halfslab import mvpraymarch_half_from_cameras, template_to_half
+                th = decout.get("template_half")
+                if th is None:
+                    th = template_to_half(decout["template"].detach())
+                rayrgba = mvpraymarch_half_from_cameras(campos, camrot, focal, princpt, pixelcoords, rm.volume_radius,
+                                                        rm.dt, prims, decout["template"], th)
+            else:
+                rayrgba = mvpraymarch_from_cameras(campos, camrot, focal, princpt, pixelcoords, rm.volume_radius, rm.dt,
+                                                   prims, decout["template"])
             cw = cb = None
             if self.colorcal is not None and have_idx:                               # colorcal.py:28-30
                 cw = self.colorcal.wcam[camindex] + self.colorcal.wident[idindex]
@@ -491,6 +516,9 @@ class RaymarchTrainModel(nn.Module):
             return {"irgbrec": irgbrec, "ialpha": ialpha, "primscale": decout["primscale"], "bg": bg,
                     "verts": decout.get("verts"), "expr_mu": expr_mu, "expr_logstd": expr_logstd,
                     "irgbl1_sum": l1sum if target is not None else None}
+        if self.half_slabs:
+            raise NotImplementedError("half_slabs=True runs on the fused GPU branch only (gfx950 kernels, fused_rays and "
+                                      "fused_tail on, no warp field)")
         if self._renderer is not None:
             rayrgb, rayalpha = self._renderer(camrot, campos, focal, princpt, pixelcoords, decout)
         elif self.fused_rays and decout.get("warp") is None:

@@ -138,6 +138,26 @@ int mvp_march_render_half(int N, int H, int W, int K, const float *raypos, const
 /* fp32 slab tensor -> fp16 (round to nearest even), `voxels` = N*K*TD*TH*TW (even).  16 B read + 8 B written per voxel. */
 int mvp_template_to_half(long long voxels, const float *tplate, void *tplate_half, void *stream);
 
+/* TRAINING over half-precision slabs (no counterpart in the reference).  The forward march of mvp_march_forward /
+ * mvp_march_forward_cams without the warp field, reading tplate_half [N,K,8,8,8,4] fp16 RGBA (the round-to-nearest-even copy
+ * of the fp32 master: mvp_template_to_half, mvp_template_assemble_frames_forward_half) and writing the same hand-off
+ * (raysat, rayaux, primlist_count, primlist) for mvp_march_backward_half.  Bit for bit what mvp_march_forward gives on the
+ * widened slabs (fp16 -> fp32 is exact and the sampler sums in the fp32 sampler's order).  8^3 slabs, else
+ * MVP_ERR_UNSUPPORTED. */
+int mvp_march_forward_half(int N, int H, int W, int K, const float *raypos, const float *raydir, float stepsize,
+                           const float *tminmax, const float *nodeaabb, const float *primpos, const float *primrot,
+                           const float *primscale, int TD, int TH, int TW, const void *tplate_half, float *rayrgba,
+                           float *raysat, uint32_t *rayaux, uint32_t *primlist_count, uint32_t *primlist,
+                           int primlist_cap, float fadescale, float fadeexp, uint32_t *diag, void *stream);
+int mvp_march_forward_cams_half(int N, int H, int W, int K, const float *campos, const float *camrot, const float *focal,
+                                const float *princpt, const float *pixelcoords /*or NULL*/, float volradius,
+                                float stepsize, const float *nodeaabb, const float *primpos, const float *primrot,
+                                const float *primscale, int TD, int TH, int TW, const void *tplate_half, float *rayrgba,
+                                float *raysat, uint32_t *rayaux, uint32_t *primlist_count, uint32_t *primlist,
+                                int primlist_cap, float *raypos_out /*or NULL*/, float *raydir_out /*or NULL*/,
+                                float *tminmax_out /*or NULL*/, float fadescale, float fadeexp, uint32_t *diag,
+                                void *stream);
+
 /* Backward march.  Replaces raymarch_backward_cuda (mvpraymarch.cpp:68-100, mvpraymarch_kernel.cu:122-207,
  * mvpraymarch_subset_kernel.h:102-216).  The four grad buffers are OVERWRITTEN (every element is written; the
  * caller need not zero-fill them, unlike mvpraymarch.py:240-246).  With the forward's hand-off buffers the
@@ -152,6 +172,15 @@ int mvp_march_backward(int N, int H, int W, int K, const float *raypos, const fl
                        const float *grad_rayrgba, float *grad_primpos, float *grad_primrot, float *grad_primscale,
                        float *grad_tplate, float *grad_warp /*NULL iff warp is NULL*/, float fadescale,
                        float fadeexp, uint32_t *diag, void *stream);
+/* The backward over the fp16 slabs the forward marched (mvp_march_forward_half / _cams_half): same owners, same hand-off,
+ * no warp field.  The gradients are the march's at the ROUNDED slab values; all four are fp32 and OVERWRITTEN, grad_tplate
+ * [N,K,8,8,8,4] included.  The primitive-centric kernel stages each slab widened to fp32. */
+int mvp_march_backward_half(int N, int H, int W, int K, const float *raypos, const float *raydir, float stepsize,
+                            const float *tminmax, const float *nodeaabb, const float *primpos, const float *primrot,
+                            const float *primscale, int TD, int TH, int TW, const void *tplate_half, const float *raysat,
+                            const uint32_t *rayaux, uint32_t *primlist_count, const uint32_t *primlist, int primlist_cap,
+                            const float *grad_rayrgba, float *grad_primpos, float *grad_primrot, float *grad_primscale,
+                            float *grad_tplate, float fadescale, float fadeexp, uint32_t *diag, void *stream);
 
 /* The decode tail and its image loss in one pass each way: colour calibration `w * image + b`
  * (models/colorcals/colorcal.py:28-31, models/autoencoder.py:254-256), matting `rayrgb + (1 - rayalpha) * bg`
@@ -204,6 +233,10 @@ int mvp_template_assemble_forward_half(int N, int nh, int B, const float *tex, c
 long long mvp_template_assemble_frames_blocks(int nh, int B);
 int mvp_template_assemble_frames_forward(int F, int nh, int B, const float *tex, const float *opacity, const float *gain,
                                          float *tplate, void *stream);
+/* ... writing fp16 RGBA slabs: gain[f] * assemble(tex, opacity) rounded to nearest even, bit for bit
+ * mvp_template_assemble_frames_forward's output cast to fp16 (the shadow slabs of the half-slab training path). */
+int mvp_template_assemble_frames_forward_half(int F, int nh, int B, const float *tex, const float *opacity,
+                                              const float *gain, void *tplate_half, void *stream);
 int mvp_template_assemble_frames_backward(int F, int nh, int B, const float *tex, const float *opacity, const float *gain,
                                           const float *grad_tplate, float *grad_tex, float *grad_opacity,
                                           float *gain_partials, void *stream);
