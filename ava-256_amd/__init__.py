@@ -5,7 +5,8 @@ Only what the path needs lives here:
   build.py         hipcc driver (in-tree build, no torch extension machinery)
   _lib.py          ctypes binding of the C-ABI (fails loudly when the library is missing)
   raydirs.py       compute_raydirs / ComputeRaydirs          (reference: extensions/utils/utils.py:21-51)
-  mvpraymarch.py   mvpraymarch / MVPRaymarch / build_accel   (reference: extensions/mvpraymarch/mvpraymarch.py:21-390)
+  mvpraymarch.py   mvpraymarch / MVPRaymarch / build_accel   (reference: extensions/mvpraymarch/mvpraymarch.py:21-390),
+                   and mvpraymarch_depth: the same march with the expected depth (Raymarcher's with_pos_img)
   raymarcher.py    Raymarcher nn.Module                      (reference: models/raymarchers/mvpraymarcher.py:17-54)
   native_shim.py   `mvpraymarchlib` / `utilslib` with the reference's positional signatures (mvpraymarch.cpp:146-405,
                    utils.cpp:46-137) over the C ABI: the reference's unmodified Python glue can bind to this build
@@ -24,9 +25,10 @@ if its tensors are not on a HIP device or if libmvp_gfx950.so has not been built
 """
 from .raydirs import ComputeRaydirs, compute_raydirs  # noqa: F401
 from .mvpraymarch import MVPRaymarch, MVPRaymarchFromCameras, build_accel, mvpraymarch, mvpraymarch_from_cameras  # noqa: F401
+from .mvpraymarch import MVPRaymarchDepth, mvpraymarch_depth  # noqa: F401
 from .raymarcher import Raymarcher  # noqa: F401
 from .halfslab import mvpraymarch_half, mvpraymarch_half_from_cameras, assemble_template_frames_half  # noqa: F401
 
 __all__ = ["compute_raydirs", "ComputeRaydirs", "mvpraymarch", "MVPRaymarch", "build_accel", "Raymarcher",
            "mvpraymarch_from_cameras", "MVPRaymarchFromCameras", "mvpraymarch_half", "mvpraymarch_half_from_cameras",
-           "assemble_template_frames_half"]
+           "assemble_template_frames_half", "mvpraymarch_depth", "MVPRaymarchDepth"]

@@ -50,6 +50,9 @@ SIGNATURES["mvp_march_forward_cams_half"] = SIGNATURES["mvp_march_forward_cams"]
 # grad_rayrgba,g_pos,g_rot,g_scale,g_tplate | fadescale,fadeexp | diag,stream
 SIGNATURES["mvp_march_backward_half"] = (_c_int, [_c_int] * 4 + [_c_void_p] * 2 + [_c_float] + [_c_void_p] * 5 + [_c_int] * 3 +
                                          [_c_void_p] * 5 + [_c_int] + [_c_void_p] * 5 + [_c_float] * 2 + [_c_void_p] * 2)
+# the expected-depth channel: mvp_march_forward / mvp_march_backward plus raydepth | raydepth, grad_raydepth at the end
+SIGNATURES["mvp_march_forward_depth"] = (_c_int, SIGNATURES["mvp_march_forward"][1] + [_c_void_p])
+SIGNATURES["mvp_march_backward_depth"] = (_c_int, SIGNATURES["mvp_march_backward"][1] + [_c_void_p] * 2)
 SIGNATURES["mvp_template_assemble_forward_half"] = (_c_int, [_c_int] * 3 + [_c_void_p] * 4)
 SIGNATURES["mvp_template_assemble_forward"] = (_c_int, [_c_int] * 3 + [_c_void_p] * 4)
 SIGNATURES["mvp_template_assemble_backward"] = (_c_int, [_c_int] * 3 + [_c_void_p] * 5)

@@ -1,6 +1,7 @@
 // march_bwd.hip -- the backward march: primitive-centric kernel (bwd_prim_kernel), its two-pass instantiation, the
-// per-packet bound prologue, and the C-ABI entry point mvp_march_backward, which also launches the ray-centric
-// kernel of march_packet.h behind them for whatever they handed over.
+// per-packet bound prologue, and the C-ABI entry points mvp_march_backward (and _half, _depth: the same owners over fp16 slabs /
+// with the expected-depth channel), which also launch the ray-centric kernel of march_packet.h behind them for whatever they
+// handed over.
 //   /root/reference/extensions/mvpraymarch/mvpraymarch.cpp:68-100 (raymarch_backward_cuda),
 //   mvpraymarch_subset_kernel.h:102-216, primaccum.h:81-98, primsampler.h:68-91, utils.h:504-643, primtransf.h:155-179
 #include "march_packet.h"
@@ -41,7 +42,10 @@ namespace mvp {
 //     G_q = max |grad_rayrgba| over the ray PACKETS of the round's list entries (packetmax_kernel, one pass over the
 //     upstream gradient before this kernel), Amax = the slab's max |opacity|; a plain sample weighs
 //     alpha * fade * dt <= Amax * dt, and the sample that saturates a ray weighs 1 - alpha_before <= its own alpha * dt (it
-//     saturated BECAUSE alpha_before + alpha * dt >= 1).  Opacity channel: B = dt * (3 (Tmax + Rmax) + 1) * G_q.
+//     saturated BECAUSE alpha_before + alpha * dt >= 1).  Opacity channel: B = dt * (3 (Tmax + Rmax) + 1) * G_q; with the
+//     expected-depth channel (DEPTH) a sample's opacity gradient also carries dt * (t - t_sat) * g_d, so B = dt * ((3 (Tmax +
+//     Rmax) + 1) * G_q + D_q), D_q = the largest depth_bound() >= |t - t_sat| * |g_d| over the rays the round's records name
+//     (phase 1; every t a ray samples lies in [tmin, tmax + 1e-5]).
 //     Resolution 2^-31 * n * B: a round of typical packets (C2: ~1200 samples) resolves 2^-20.8 of the bound; rounds are
 //     cut so that n <= 2^14 (a round takes fewer list entries when the packets' step ranges are long).
 //   * DYNAMIC RANGE.  One word resolves the round's contributions relative to the LARGEST upstream gradient near it.
@@ -170,6 +174,13 @@ __device__ __forceinline__ int fix_rn(float v) {
 // (The encoders that use it stay macros at their call sites: as functions they change the scatter's code -- see there.)
 #define MVP_PACK2(LO_, HI_) ((unsigned long long)(uint32_t)(LO_) | ((unsigned long long)(uint32_t)((HI_) + ((LO_) >> 31)) << 32))
 
+// (DEPTH) Bound of a ray's depth term divided by dt, |t - t_sat| * |grad_raydepth|: every t the ray samples -- t_sat included --
+// lies in [tmin, tmax + 1e-5] (subset_kernel.h:84), so |t - t_sat| <= 2 (max(|tmin|, |tmax|) + 1e-5); the factor 1.0001 covers the
+// roundings of t and of the product.  NaN / Inf stay non-finite (the bound test then hands the primitive over).
+__device__ __forceinline__ float depth_bound(float gdep, float2 tt) {
+    return 2.0002f * (fmaxf(fabsf(tt.x), fabsf(tt.y)) + 1e-5f) * fabsf(gdep);
+}
+
 // (WARP, round 6: the zero padding is evaluated without branches, as zero weights on cells the sample reads anyway --
 //  march_common.h: tri_zero_pad.)
 // TS > 0: the slab is TS^3 (compile-time strides: the 32 atomics and 8 reads of a sample share ONE address register and
@@ -180,10 +191,14 @@ constexpr int kBwdOcc = 3;  // waves per SIMD the register allocation aims at (4
 // RESID: the two-pass instantiation (header, DYNAMIC RANGE): owns the primitives the plain one marked, nothing else.
 // HSLAB: p.tplate holds fp16 RGBA slabs (8 bytes per voxel, 8^3): staged widened to fp32, so the LDS slab -- and everything
 // after staging, the bounds included -- is what the fp32 instantiation sees on template_half.float().
-template <bool FADE8, int TS, int PW, bool WARP, bool RESID, bool HSLAB = false>
-__device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int block, float4 *smem4) {
+// DEPTH: the expected-depth channel (march_packet.h's DEPTH; da.grad_raydepth): every sample's opacity gradient gains
+// dt * (t - t_sat) * grad_raydepth, and the opacity bound grows by dt * D_q (header).
+template <bool FADE8, int TS, int PW, bool WARP, bool RESID, bool HSLAB = false, bool DEPTH = false>
+__device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int block, float4 *smem4,
+                                              const DepthArgs &da = DepthArgs{}) {
     static_assert(!WARP || TS == 0, "the warp-field variant uses run-time slab dimensions");
     static_assert(!HSLAB || !WARP, "fp16 slabs: no warp field");
+    static_assert(!DEPTH || (!WARP && !HSLAB), "depth: fp32 slabs, no warp field");
     constexpr int kPrimWaves = PW, kPrimBlock = PW * 64;
     constexpr int kEntriesPerRound = prim_entries_per_round(PW), kQueueCap = prim_queue_cap(PW);
     const int TD = TS ? TS : p.TD, TH = TS ? TS : p.TH, TW = TS ? TS : p.TW;
@@ -200,6 +215,7 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
     uint32_t *s_bucket = s_qn + 4;  // kLenBuckets words
     uint16_t *s_perm = reinterpret_cast<uint16_t *>(s_bucket + kLenBuckets);  // pl_cap entries: list index by rank
     uint32_t *s_gext = reinterpret_cast<uint32_t *>(s_red + 62);  // per round: bits(max), bits(min) of the queued rays' max |g|
+    uint32_t *s_dext = reinterpret_cast<uint32_t *>(s_red + 61);  // (DEPTH) per round: bits(D_q), see the header
     // WARP: [warp grid as float4 (x,y,z,-)] [VWp] int64 (x | y) sums, [VWp] int32 z sums -- behind everything else (16-byte
     // aligned: the host sizes the part above as a multiple of 16 bytes)
     const int WD = WARP ? p.WD : 2, WH = WARP ? p.WH : 2, WW = WARP ? p.WW : 2;
@@ -359,6 +375,7 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
     const size_t img = (size_t)n * p.H * p.W;
     const float *raypos_n = p.raypos + img * 3, *raydir_n = p.raydir + img * 3, *tminmax_n = p.tminmax + img * 2;
     const float *grad_n = p.grad_rayrgba + img * 4, *raysat_n = p.raysat_in + img * 3;
+    const float *gdep_n = DEPTH ? da.grad_raydepth + img : nullptr;
     const uint32_t *aux_n = p.rayaux + img * 4;
     const int sW = 1, sH = TW, sD = TH * TW;  // voxel strides of the template slab
     const float mx = 0.5f * (float)(TW - 1), my = 0.5f * (float)(TH - 1), mz = 0.5f * (float)(TD - 1);
@@ -435,6 +452,9 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
     for (uint32_t ebase = 0; ebase < cnt;) {
         if (tid < kLenBuckets) s_bucket[tid] = 0u;
         if (tid == 0) s_qn[1] = 0u, s_gext[0] = 0u, s_gext[1] = 0x7fffffffu;
+        if constexpr (DEPTH) {
+            if (tid == 0) s_dext[0] = 0u;
+        }
         __syncthreads();
         // The transform is block-uniform and lives in SGPRs.  Made opaque once per round, so that packed-math operand
         // pairs built from it are re-made here (a v_mov each) instead of being carried, spilled, across the march.
@@ -458,6 +478,7 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
         bool toolong = false;
         uint32_t mylen = 0u;
         uint32_t gq_hi = 0u;  // bits of the largest max |grad_rayrgba| over the packets this wave's records name (wave-uniform)
+        uint32_t dq_hi = 0u;  // (DEPTH) bits of the largest depth bound depth_bound() over the rays they name
         uint32_t ncmp = 0u;   // rays named by this wave's entries (wave-uniform, <= kEntriesPerWave * 64)
         uint2 *s_cmp = s_q + wave * (kEntriesPerWave * 64);
         {
@@ -514,6 +535,7 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
                     const float2 tt = *at_bytes<float2>(tminmax_n, r * 8u);
                     const uint4 ax = *at_bytes<uint4>(aux_n, r * 16u);  // {key of the saturating sample, -, first step, -}
                     const int incs = (int)ax.z;
+                    if constexpr (DEPTH) dq_hi = max(dq_hi, abs_bits(depth_bound(*at_bytes<float>(gdep_n, r * 4u), tt)));
                     // the same formulas the forward used for the packet range [elo, ehi] (the union of these over lanes)
                     const f3 r0 = rot_rows(q, o - q.pos) * q.scale, rd = rot_rows(q, d) * q.scale;
                     const f3 ird = mk3(fast_rcp(rd.x), fast_rcp(rd.y), fast_rcp(rd.z));
@@ -557,19 +579,28 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
                 if (wl > 0.f) atomicAdd(s_qn + 1, (uint32_t)wl);
                 if (gq_hi != 0u) atomicMax(s_gext, gq_hi);
             }
+            if constexpr (DEPTH) {
+                dq_hi = (uint32_t)wave_max((int)dq_hi);  // (patterns < 2^31: signed order)
+                if (lane == 0 && dq_hi != 0u) atomicMax(s_dext, dq_hi);
+            }
         }
         __syncthreads();
         // ---------------- this round's bound and scales (header) ----------------
         const uint32_t round_samples = (uint32_t)uni((int)s_qn[1]);  // exact; <= kQueueCap * 127 < 2^17
         const uint32_t gq_bits = (uint32_t)uni((int)s_gext[0]);
         const float Gq = __uint_as_float(gq_bits);
+        const uint32_t dq_bits = DEPTH ? (uint32_t)uni((int)s_dext[0]) : 0u;
+        const float Dq = __uint_as_float(dq_bits);
         bool bad_bound = false;
         float res_mul = 1.f;  // pass B: residuals (|r| <= 1/2) times this
         s_rgb = s_a = s_w = 1.f;
-        if (round_samples > 0u && gq_bits != 0u) {  // (G_q = 0: every marched ray is skipped, scales are irrelevant)
-            const float Brgb = wrgb * Gq, Ba = fa * Gq, Bw = WARP ? fw * Gq : 1.f;
+        if (round_samples > 0u && (gq_bits | dq_bits) != 0u) {  // (both 0: every marched ray is skipped, scales are irrelevant)
+            // (DEPTH: with G_q = 0 the colour contributions are exact zeros and any finite scale serves -- D_q's)
+            const float Brgb = wrgb * ((DEPTH && gq_bits == 0u) ? Dq : Gq), Ba = DEPTH ? fa * Gq + dt * Dq : fa * Gq,
+                        Bw = WARP ? fw * Gq : 1.f;
             bad_bound = gq_bits >= 0x7f800000u || !(Brgb < 1.0e30f) || !(Ba < 1.0e30f) || !(Brgb > 1.0e-30f) ||
                         !(Ba > 1.0e-30f) || !(Bw < 1.0e30f);
+            if constexpr (DEPTH) bad_bound = bad_bound || dq_bits >= 0x7f800000u;
             // (v_rcp_f32, 1 ulp: a scale need not be an exact quotient -- the sums are decoded with the reciprocal of the scale
             //  that was applied, and kFixRange keeps 0.1 % of headroom; five IEEE divisions per wave and round were 1.2 % of
             //  the kernel's instructions)
@@ -673,6 +704,7 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
             const uint32_t slot = it.x >> 23;
             f3 o = mk3(0.f, 0.f, 0.f), d = mk3(0.f, 0.f, 1.f);
             float tmin = 0.f;
+            float gdep = 0.f, tsat0 = 0.f;  // (DEPTH) grad_raydepth; t of the saturating sample, 0 when the ray did not saturate
             f3 dL3 = mk3(0.f, 0.f, 0.f), rsat = mk3(-1.f, -1.f, -1.f);
             float dLw = 0.f, wbefore = 0.f, tend = -INFINITY;
             uint32_t satkey = 0u;
@@ -685,14 +717,21 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
                 dLw = g4.w;
                 // bits of this ray's max |upstream gradient| (non-negative floats order like uints).  Zero: the ray adds
                 // exact zeros to every gradient -- not marched
-                const uint32_t gb = max(max(__float_as_uint(g4.x) & 0x7fffffffu, __float_as_uint(g4.y) & 0x7fffffffu),
-                                        max(__float_as_uint(g4.z) & 0x7fffffffu, __float_as_uint(g4.w) & 0x7fffffffu));
+                uint32_t gb = max(max(__float_as_uint(g4.x) & 0x7fffffffu, __float_as_uint(g4.y) & 0x7fffffffu),
+                                  max(__float_as_uint(g4.z) & 0x7fffffffu, __float_as_uint(g4.w) & 0x7fffffffu));
+                if constexpr (DEPTH) {  // (and the depth term's bound: the dynamic-range test below compares with max(G_q, D_q))
+                    gdep = *at_bytes<float>(gdep_n, r * 4u);
+                    gb = max(gb, abs_bits(depth_bound(gdep, *at_bytes<float2>(tminmax_n, r * 8u))));
+                }
                 if (gb == 0u) len = 0; else gq_lo = min(gq_lo, gb);
                 rsat = ld3(at_bytes<float>(raysat_n, r * 12u));
                 const uint4 aux = *at_bytes<uint4>(aux_n, r * 16u);
                 satkey = aux.x;
                 wbefore = __uint_as_float(aux.y);
                 tend = __uint_as_float(aux.w);
+                if constexpr (DEPTH) {
+                    if (rsat.x > -1.f) tsat0 = fmaf((float)(satkey >> 9), dt, tmin);  // (has_sat) satkey = (step << 9) | slot
+                }
             }
             const bool has_sat = rsat.x > -1.f;  // primaccum.h:93
             const int nsteps = uni(wave_max(len));
@@ -924,6 +963,9 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
                     wbad = wbad || !(fabsf(weight) <= wmax);  // outside the fixed-point bound (signed opacity) or NaN
                     float4 dLs;
                     sample_dls(dLs, weight, issat, v, dt, dL3, dLw, rsat, has_sat);
+                    if constexpr (DEPTH) {  // the colour channels' rule with t for the colour (t_sat for raysat)
+                        if (!issat) dLs.w = fmaf(dt * (t - tsat0), gdep, dLs.w);
+                    }
                     f3 gy = fade_grad(dLs, alpha, fade, ypow, p.fadescale, p.fadeexp);
                     const v2f dl = {dLs.x, dLs.y}, dh = {dLs.z, dLs.w};
 #define MVP_DOT4(NAME_, C_)                                 \
@@ -1030,7 +1072,7 @@ __device__ __forceinline__ void bwd_prim_body(const MarchParams &p, const int bl
                 pass_b = true;
                 continue;
             }
-        } else if (__uint_as_float((uint32_t)uni((int)s_gext[1])) * kTwoPassRatio < Gq) {
+        } else if (__uint_as_float((uint32_t)uni((int)s_gext[1])) * kTwoPassRatio < (DEPTH ? fmaxf(Gq, Dq) : Gq)) {
             // (rare: header, DYNAMIC RANGE) the rays marched here are more than 256x below the round's bound: the two-pass
             // instantiation, launched behind this kernel, owns the primitive and overwrites every output
             if (tid == 0) {
@@ -1158,6 +1200,13 @@ __global__ __launch_bounds__(PW * 64, kBwdOcc) void bwd_prim_hslab_kernel(const 
     bwd_prim_body<FADE8, 8, PW, false, false, true>(p, (int)blockIdx.x, smem4);
 }
 
+// The same with the expected-depth channel (fp32 slabs, no warp field)
+template <bool FADE8, int TS, int PW>
+__global__ __launch_bounds__(PW * 64, kBwdOcc) void bwd_prim_depth_kernel(const MarchParams p, const DepthArgs da) {
+    extern __shared__ __attribute__((aligned(16))) float4 smem4[];
+    bwd_prim_body<FADE8, TS, PW, false, false, false, true>(p, (int)blockIdx.x, smem4, da);
+}
+
 // The two-pass instantiation (general slab strides): a small persistent grid that walks the same block -> primitive
 // map and works only on the primitives the kernel above marked; returns at once when it marked none.  kPreciseWaves waves per
 // workgroup: the marked primitives are few and LARGE (tens of thousands of samples each, marched twice), one per workgroup
@@ -1232,6 +1281,40 @@ __global__ __launch_bounds__(kPreciseWaves * 64, 2) void bwd_prim_precise_hslab_
     }
 }
 
+// ... with the expected-depth channel
+template <bool FADE8>
+__global__ __launch_bounds__(kPreciseWaves * 64, 2) void bwd_prim_precise_depth_kernel(const MarchParams p, const int total_blocks,
+                                                                                      const DepthArgs da) {
+    extern __shared__ __attribute__((aligned(16))) float4 smem4[];
+    if ((p.pl_count[(size_t)p.N * p.K] & kFlagBwdPrecise) == 0u) return;
+    constexpr int kTodo = 256;  // (the marked blocks of this workgroup, found in one parallel sweep: bwd_prim_precise_kernel)
+    __shared__ int s_todo[kTodo];
+    __shared__ int s_ntodo;
+    if (threadIdx.x == 0) s_ntodo = 0;
+    __syncthreads();
+    for (int b = (int)blockIdx.x + (int)threadIdx.x * (int)gridDim.x; b < total_blocks; b += (int)(blockDim.x * gridDim.x)) {
+        int n, k;
+        if (!prim_of_block(p, b, n, k)) continue;
+        const uint32_t c = p.pl_count[(size_t)n * p.K + k];
+        if ((c & (kCountPrecise | kCountDead)) != kCountPrecise) continue;
+        const int slot = atomicAdd(&s_ntodo, 1);
+        if (slot < kTodo) s_todo[slot] = b;
+    }
+    __syncthreads();
+    const int ntodo = s_ntodo;
+    if (ntodo > kTodo) {
+        for (int b = (int)blockIdx.x; b < total_blocks; b += (int)gridDim.x) {
+            bwd_prim_body<FADE8, 0, kPreciseWaves, false, true, false, true>(p, b, smem4, da);
+            __syncthreads();
+        }
+        return;
+    }
+    for (int i = 0; i < ntodo; ++i) {
+        bwd_prim_body<FADE8, 0, kPreciseWaves, false, true, false, true>(p, s_todo[i], smem4, da);
+        __syncthreads();
+    }
+}
+
 }  // namespace mvp
 
 // hslab: tplate points at fp16 RGBA slabs (mvp_march_backward_half: 8^3, no warp field)
@@ -1241,10 +1324,17 @@ static int march_backward_impl(int N, int H, int W, int K, const float *raypos, 
                                const float *warp, const float *raysat, const uint32_t *rayaux, uint32_t *primlist_count,
                                const uint32_t *primlist, int primlist_cap, const float *grad_rayrgba, float *grad_primpos,
                                float *grad_primrot, float *grad_primscale, float *grad_tplate, float *grad_warp,
-                               float fadescale, float fadeexp, uint32_t *diag, void *stream, bool hslab) {
+                               float fadescale, float fadeexp, uint32_t *diag, void *stream, bool hslab,
+                               const float *grad_raydepth = nullptr) {
     using namespace mvp;
     MarchParams p = {};
     if (hslab && (warp || grad_warp)) return MVP_ERR_BADARG;
+    // depth (mvp_march_backward_depth): fp32 slabs, no warp field, and the forward's rayaux (every owner reads the saturating
+    // sample's step from it)
+    const bool depth = grad_raydepth != nullptr;
+    if (depth && (hslab || warp || grad_warp)) return MVP_ERR_BADARG;
+    if (depth && (long long)N * H * W > 0 && (!rayaux || !aligned16(rayaux))) return MVP_ERR_BADARG;
+    const DepthArgs da = {nullptr, grad_raydepth};
     if (hslab && K > 0 && (TD != 8 || TH != 8 || TW != 8 || (unsigned long long)K * 4096ull >= (1ull << 32)))
         return MVP_ERR_UNSUPPORTED;
     p.N = N, p.H = H, p.W = W, p.K = K, p.TD = TD, p.TH = TH, p.TW = TW;
@@ -1319,6 +1409,13 @@ static int march_backward_impl(int N, int H, int W, int K, const float *raypos, 
         else                                                                                       \
             hipLaunchKernelGGL((bwd_prim_kernel<F8_, TS_, 2>), grid, block, lds, st, p);           \
     }
+#define MVP_LAUNCH_PRIMD(F8_, TS_)                                                                 \
+    {                                                                                              \
+        if (pw == 3)                                                                               \
+            hipLaunchKernelGGL((bwd_prim_depth_kernel<F8_, TS_, 3>), grid, block, lds, st, p, da); \
+        else                                                                                       \
+            hipLaunchKernelGGL((bwd_prim_depth_kernel<F8_, TS_, 2>), grid, block, lds, st, p, da); \
+    }
 #define MVP_LAUNCH_PRIMW(F8_)                                                                      \
     {                                                                                              \
         if (pw == 3)                                                                               \
@@ -1326,7 +1423,16 @@ static int march_backward_impl(int N, int H, int W, int K, const float *raypos, 
         else                                                                                       \
             hipLaunchKernelGGL((bwd_prim_kernel<F8_, 0, 2, true>), grid, block, lds, st, p);       \
     }
-        if (hslab) {
+        if (depth) {
+            if (fade8 && cube8)
+                MVP_LAUNCH_PRIMD(true, 8)
+            else if (fade8)
+                MVP_LAUNCH_PRIMD(true, 0)
+            else if (cube8)
+                MVP_LAUNCH_PRIMD(false, 8)
+            else
+                MVP_LAUNCH_PRIMD(false, 0)
+        } else if (hslab) {
             if (pw == 3 && fade8)
                 hipLaunchKernelGGL((bwd_prim_hslab_kernel<true, 3>), grid, block, lds, st, p);
             else if (pw == 3)
@@ -1349,6 +1455,7 @@ static int march_backward_impl(int N, int H, int W, int K, const float *raypos, 
             MVP_LAUNCH_PRIM(false, 0)
 #undef MVP_LAUNCH_PRIM
 #undef MVP_LAUNCH_PRIMW
+#undef MVP_LAUNCH_PRIMD
         rc = launch_status();
         if (rc != MVP_OK) return rc;
         {  // the two-pass instantiation for the primitives that kernel marked (heavy-tailed upstream gradients); exits at
@@ -1363,7 +1470,11 @@ static int march_backward_impl(int N, int H, int W, int K, const float *raypos, 
                 lds2 += VW * 16 + VWp * 12;
             }
             const dim3 g2((unsigned)(pb < 2048 ? pb : 2048)), b2(kPreciseWaves * 64);
-            if (hslab && fade8)
+            if (depth && fade8)
+                hipLaunchKernelGGL((bwd_prim_precise_depth_kernel<true>), g2, b2, lds2, st, p2, (int)pb, da);
+            else if (depth)
+                hipLaunchKernelGGL((bwd_prim_precise_depth_kernel<false>), g2, b2, lds2, st, p2, (int)pb, da);
+            else if (hslab && fade8)
                 hipLaunchKernelGGL((bwd_prim_precise_hslab_kernel<true>), g2, b2, lds2, st, p2, (int)pb);
             else if (hslab)
                 hipLaunchKernelGGL((bwd_prim_precise_hslab_kernel<false>), g2, b2, lds2, st, p2, (int)pb);
@@ -1384,7 +1495,12 @@ static int march_backward_impl(int N, int H, int W, int K, const float *raypos, 
     int fb = p.total_packets;
     if (!p.fallback_all && fb > 256 * 16) fb = 256 * 16;  // persistent-style grid for the rarely-taken path
     const dim3 grid((unsigned)fb), block(kWave);
-    if (hslab) {
+    if (depth) {
+        if (fade8)
+            hipLaunchKernelGGL((march_depth_kernel<true, true>), grid, block, 0, st, p, da);
+        else
+            hipLaunchKernelGGL((march_depth_kernel<true, false>), grid, block, 0, st, p, da);
+    } else if (hslab) {
         if (fade8)
             hipLaunchKernelGGL((march_hslab_kernel<true, true>), grid, block, 0, st, p);
         else
@@ -1432,4 +1548,25 @@ extern "C" int mvp_march_backward_half(int N, int H, int W, int K, const float *
                                TW, reinterpret_cast<const float *>(tplate_half), 0, 0, 0, nullptr, raysat, rayaux,
                                primlist_count, primlist, primlist_cap, grad_rayrgba, grad_primpos, grad_primrot,
                                grad_primscale, grad_tplate, nullptr, fadescale, fadeexp, diag, stream, true);
+}
+
+// mvp_march_backward with the expected-depth channel of mvp_march_forward_depth: grad_raydepth [N,H,W] is the upstream gradient of
+// its raydepth.  Same owners, hand-off and outputs as mvp_march_backward; warp / grad_warp must be NULL and rayaux is required.
+// raydepth (the forward's output) is validated but not read: the depth term needs only the t of each ray's saturating sample,
+// which the rayaux record names.
+extern "C" int mvp_march_backward_depth(int N, int H, int W, int K, const float *raypos, const float *raydir,
+                                        float stepsize, const float *tminmax, const float *nodeaabb,
+                                        const float *primpos, const float *primrot, const float *primscale, int TD,
+                                        int TH, int TW, const float *tplate, int WD, int WH, int WW, const float *warp,
+                                        const float *raysat, const uint32_t *rayaux, uint32_t *primlist_count,
+                                        const uint32_t *primlist, int primlist_cap, const float *grad_rayrgba,
+                                        float *grad_primpos, float *grad_primrot, float *grad_primscale,
+                                        float *grad_tplate, float *grad_warp, float fadescale, float fadeexp,
+                                        uint32_t *diag, void *stream, const float *raydepth, const float *grad_raydepth) {
+    if ((long long)N * H * W > 0 && (!raydepth || !grad_raydepth)) return MVP_ERR_BADARG;
+    if (!grad_raydepth) return MVP_ERR_BADARG;
+    return march_backward_impl(N, H, W, K, raypos, raydir, stepsize, tminmax, nodeaabb, primpos, primrot, primscale, TD, TH,
+                               TW, tplate, WD, WH, WW, warp, raysat, rayaux, primlist_count, primlist, primlist_cap,
+                               grad_rayrgba, grad_primpos, grad_primrot, grad_primscale, grad_tplate, grad_warp, fadescale,
+                               fadeexp, diag, stream, false, grad_raydepth);
 }

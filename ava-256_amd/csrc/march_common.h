@@ -105,6 +105,13 @@ struct MarchParams {
     int debug_stage;      // profiling (MVP_DEBUG_STAGE): 11 stop after the root test, 12 after the ancestor pre-cull,
                           // 13 after the implicit level, 1 after traversal, 2 after the exact pass, 3 no sampling
 };
+// The expected-depth output (DEPTH instantiations only: march_depth_kernel, bwd_prim_depth_kernel, bwd_prim_precise_depth_kernel;
+// mvp_march_forward_depth / mvp_march_backward_depth).  A kernel argument of its own, so that MarchParams -- and with it the
+// argument layout and code of every other kernel -- stays as it is.  raydepth = sum_i contrib_i * t_i per ray, [N,H,W].
+struct DepthArgs {
+    float *raydepth;              // forward output
+    const float *grad_raydepth;   // backward input
+};
 #ifdef MVP_DEBUG_HOOKS
 #define MVP_DEBUG_STAGE(P_) ((P_).debug_stage)
 #define MVP_DEBUG_FORCE_DFS(P_) ((P_).debug_force_dfs != 0)

@@ -1,6 +1,7 @@
 // march_fwd.hip -- C-ABI entry points of the forward march (include/mvp_abi.h: mvp_march_forward,
-// mvp_march_forward_cams, mvp_march_render_half, mvp_march_forward_half, mvp_march_forward_cams_half) and the
-// instantiations of march_kernel<false, ..> (march_half_kernel, march_hslab_kernel<false, ..>) they launch.
+// mvp_march_forward_cams, mvp_march_render_half, mvp_march_forward_half, mvp_march_forward_cams_half,
+// mvp_march_forward_depth) and the instantiations of march_kernel<false, ..> (march_half_kernel,
+// march_hslab_kernel<false, ..>, march_depth_kernel<false, ..>) they launch.
 //   /root/reference/extensions/mvpraymarch/mvpraymarch.cpp:38-66 (raymarch_forward_cuda), mvpraymarch_kernel.cu:35-120
 #include "march_packet.h"
 
@@ -16,9 +17,12 @@ static int march_forward_impl(int N, int H, int W, int K, const float *raypos, c
                               const float *tplate, int WD, int WH, int WW, const float *warp, float *rayrgba,
                               float *raysat, uint32_t *rayaux, uint32_t *primlist_count, uint32_t *primlist,
                               int primlist_cap, float fadescale, float fadeexp, uint32_t *diag, void *stream,
-                              bool half_slabs = false, bool hslab_train = false) {
+                              bool half_slabs = false, bool hslab_train = false, float *raydepth = nullptr) {
     using namespace mvp;
     MarchParams p = {};
+    if (raydepth) {  // the expected-depth channel (mvp_march_forward_depth): fp32 slabs, rays as tensors, no warp field
+        if (warp || cams || half_slabs || hslab_train) return MVP_ERR_BADARG;
+    }
     if (hslab_train) {  // fp16 RGBA slabs with the hand-off to mvp_march_backward_half: 8^3 slabs, no warp field
         if (warp) return MVP_ERR_BADARG;
         if (K > 0 && (TD != 8 || TH != 8 || TW != 8 || (unsigned long long)K * 4096ull >= (1ull << 32)))
@@ -50,11 +54,13 @@ static int march_forward_impl(int N, int H, int W, int K, const float *raypos, c
     if (rc == 1) return MVP_OK;
     if (rc != MVP_OK) return rc;
     if (!rayrgba || !aligned16(rayrgba)) return MVP_ERR_BADARG;
+    const mvp::DepthArgs da = {raydepth, nullptr};
     if ((primlist_count != nullptr) != (primlist != nullptr)) return MVP_ERR_BADARG;
     hipStream_t st = (hipStream_t)stream;
     if (K == 0) {  // nothing to march through: all-zero image; raysat would need a -1 fill (never on the training path)
         if (raysat) return MVP_ERR_UNSUPPORTED;
         hipError_t e = hipMemsetAsync(rayrgba, 0, sizeof(float) * 4 * (size_t)N * H * W, st);
+        if (e == hipSuccess && raydepth) e = hipMemsetAsync(raydepth, 0, sizeof(float) * (size_t)N * H * W, st);
         return e == hipSuccess ? MVP_OK : (int)e;
     }
     if (p.pl_count) {
@@ -89,6 +95,16 @@ static int march_forward_impl(int N, int H, int W, int K, const float *raypos, c
             hipLaunchKernelGGL((march_hslab_kernel<false, true>), grid, block, 0, st, p);
         else
             hipLaunchKernelGGL((march_hslab_kernel<false, false>), grid, block, 0, st, p);
+    } else if (raydepth) {
+        const bool cube8 = TD == 8 && TH == 8 && TW == 8 && (unsigned long long)K * 8192ull < (1ull << 32);
+        if (fade8 && cube8)
+            hipLaunchKernelGGL((march_depth_kernel<false, true, 8>), grid, block, 0, st, p, da);
+        else if (fade8)
+            hipLaunchKernelGGL((march_depth_kernel<false, true>), grid, block, 0, st, p, da);
+        else if (cube8)
+            hipLaunchKernelGGL((march_depth_kernel<false, false, 8>), grid, block, 0, st, p, da);
+        else
+            hipLaunchKernelGGL((march_depth_kernel<false, false>), grid, block, 0, st, p, da);
     } else {
         // the reference's slab size (and BASELINE's) gets compile-time strides and 32-bit slab offsets
         const bool cube8 = TD == 8 && TH == 8 && TW == 8 && (unsigned long long)K * 8192ull < (1ull << 32);
@@ -181,4 +197,20 @@ extern "C" int mvp_march_forward_cams_half(int N, int H, int W, int K, const flo
                               primscale, TD, TH, TW, reinterpret_cast<const float *>(tplate_half), 0, 0, 0, nullptr, rayrgba,
                               raysat, rayaux, primlist_count, primlist, primlist_cap, fadescale, fadeexp, diag, stream,
                               false, true);
+}
+
+// mvp_march_forward with the expected-depth channel: raydepth [N,H,W] = sum over the ray's samples of contrib * t (premultiplied
+// by alpha like the colour; 0 where the ray hits nothing).  fp32 slabs, no warp field (warp must be NULL).  rayrgba, raysat and
+// the hand-off are bit for bit those of mvp_march_forward; mvp_march_backward_depth needs rayaux.
+extern "C" int mvp_march_forward_depth(int N, int H, int W, int K, const float *raypos, const float *raydir,
+                                       float stepsize, const float *tminmax, const float *nodeaabb, const float *primpos,
+                                       const float *primrot, const float *primscale, int TD, int TH, int TW,
+                                       const float *tplate, int WD, int WH, int WW, const float *warp, float *rayrgba,
+                                       float *raysat, uint32_t *rayaux, uint32_t *primlist_count, uint32_t *primlist,
+                                       int primlist_cap, float fadescale, float fadeexp, uint32_t *diag, void *stream,
+                                       float *raydepth) {
+    if (!raydepth || warp) return MVP_ERR_BADARG;
+    return march_forward_impl(N, H, W, K, raypos, raydir, nullptr, stepsize, tminmax, nodeaabb, primpos, primrot,
+                              primscale, TD, TH, TW, tplate, WD, WH, WW, warp, rayrgba, raysat, rayaux, primlist_count,
+                              primlist, primlist_cap, fadescale, fadeexp, diag, stream, false, false, raydepth);
 }

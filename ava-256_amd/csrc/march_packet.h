@@ -14,9 +14,14 @@ __device__ __forceinline__ void packet_sync() { __syncthreads(); }
 // HSLAB (TS > 0, no warp field): p.tplate points at fp16 RGBA slabs, 8 bytes per voxel.  The forward samples them with
 // sample_slab_hw (with RENDER: sample_slab_h), the ray-centric backward widens its corners (load_vox_h).
 // RENDER (forward, HSLAB): the render path -- no hand-off to a backward: no list records, no raysat / rayaux, no NaN tracking.
-template <bool BWD, bool FADE8, bool WARP, int TS, bool HSLAB = false, bool RENDER = false>
+// DEPTH (fp32 slabs, no warp field): the expected termination depth as a fifth composited channel whose sample value is the
+// lattice t itself.  Forward: raydepth = sum contrib * t.  Backward: the opacity gradient of a sample gains
+// dt * (t - t_sat) * grad_raydepth (t_sat = 0 for a ray that did not saturate), the colour channels' rule with t in place of
+// the sampled colour; t_sat is the t of the sample the forward's rayaux record names.
+template <bool BWD, bool FADE8, bool WARP, int TS, bool HSLAB = false, bool RENDER = false, bool DEPTH = false>
 __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, int *s_a, int *s_b, float4 *s_rec,
-                                             uint32_t *s_tab, const bool emit_all) {
+                                             uint32_t *s_tab, const bool emit_all, const DepthArgs &da = DepthArgs{}) {
+    static_assert(!DEPTH || (!WARP && !HSLAB && !RENDER), "depth: fp32 slabs, no warp field");
     constexpr bool FAST = !BWD;  // the lane-independent sweep exists for the forward only (round 6: the warp-field one too)
     const int lane = lane_id();
     const unsigned long long lt = lanemask_lt(lane);
@@ -72,6 +77,7 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
     const bool active = inimg && (tmin < tmax + 1e-5f);
 
     float4 rgba = make_float4(0.f, 0.f, 0.f, 0.f);
+    float depth = 0.f;  // (DEPTH) sum contrib * t
     f3 raysat = mk3(-1.f, -1.f, -1.f);
     uint32_t satkey = kNoSat;  // (step << 9) | list slot of the saturating sample
     float wbefore = 0.f;       // alpha just before it
@@ -455,6 +461,13 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
         rsat_in = ld3(p.raysat_in + r * 3);
     }
     const bool has_sat = rsat_in.x > -1.f;  // primaccum.h:93
+    float gdep = 0.f, tsat0 = 0.f;  // (DEPTH backward) grad_raydepth; t of the saturating sample, 0 when the ray did not saturate
+    if constexpr (BWD && DEPTH) {
+        if (inimg) {
+            gdep = da.grad_raydepth[r];
+            if (has_sat) tsat0 = lattice_t((int)(p.rayaux[r * 4] >> 9), dt, tmin);  // satkey = (step << 9) | slot
+        }
+    }
 
     if (nh > 0) {
         if (p.diag && lane == 0) {
@@ -488,6 +501,7 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
             bool work = has && ncross > 0;
             v2f xxy = oxy;
             float xz = o.z;
+            float ts = 0.f;  // (DEPTH) t of step s
             while (__ballot(work) != 0ull) {
                 if (work) {
                     if (cur == 0u) {  // step s is done: next step with an open crossing
@@ -508,6 +522,7 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
                             if (t < tend) {  // subset_kernel.h:84; t only grows from here
                                 cur = act;
                                 ray_point(oxy, o.z, dxy, d.z, t, xxy, xz);
+                                if constexpr (DEPTH) ts = t;
                             } else {
                                 work = false;
                             }
@@ -553,6 +568,7 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
                                 wbefore = rgba.w - contrib;
                                 work = false;
                             }
+                            if constexpr (DEPTH) depth = __builtin_fmaf(ts, contrib, depth);
                         }
                     }
                 }
@@ -656,6 +672,7 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
                                     wbefore = rgba.w - contrib;
                                     mine = 0ull;  // saturated: nothing after this sample is evaluated
                                 }
+                                if constexpr (DEPTH) depth = __builtin_fmaf(t, contrib, depth);
                             }
                         }
                         continue;
@@ -830,6 +847,9 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
                                             : dt * ((v.x - (has_sat ? rsat_in.x : 0.f)) * dL3.x +
                                                     (v.y - (has_sat ? rsat_in.y : 0.f)) * dL3.y +
                                                     (v.z - (has_sat ? rsat_in.z : 0.f)) * dL3.z + (has_sat ? 0.f : dLw));
+                                if constexpr (DEPTH) {
+                                    if (!sat) dLs.w = __builtin_fmaf(dt * (t - tsat0), gdep, dLs.w);
+                                }
                                 rgba.x += v.x * weight;
                                 rgba.y += v.y * weight;
                                 rgba.z += v.z * weight;
@@ -1002,6 +1022,7 @@ __device__ __forceinline__ void march_packet(const MarchParams &p, const int b, 
     }
     if (!BWD && inimg) {
         reinterpret_cast<float4 *>(p.rayrgba)[r] = rgba;  // primaccum.h:51-56
+        if constexpr (DEPTH) MVP_STREAM_STOREF(da.raydepth + r, depth);
         if constexpr (RENDER) return;   // (render path: nothing is handed to a backward)
         if (p.raysat) {
             float *sp = p.raysat + r * 3;
@@ -1085,6 +1106,34 @@ __global__ __launch_bounds__(kWave) void march_hslab_kernel(const MarchParams p)
         }
     } else {
         march_packet<BWD, FADE8, false, 8, true>(p, blockIdx.x, s_a, s_b, s_rec, s_tab, true);
+    }
+}
+
+// DEPTH: march_kernel (fp32 slabs, no warp field) with the expected-depth channel -- the forward (BWD = false) writes
+// raydepth as well, the ray-centric backward (BWD = true) adds the depth term to every sample's opacity gradient.
+template <bool BWD, bool FADE8, int TS = 0>
+__global__ __launch_bounds__(kWave) void march_depth_kernel(const MarchParams p, const DepthArgs da) {
+    constexpr int kSlowWords = kRecSlots * 16 + 2 * kMaxList;
+    constexpr int kFastWords = kFastSlots * 16 + kFastCross * kWave;
+    constexpr int kWords = (!BWD && kFastWords > kSlowWords) ? kFastWords : kSlowWords;
+    __shared__ __attribute__((aligned(16))) uint32_t smem[kWords];
+    float4 *s_rec = reinterpret_cast<float4 *>(smem);
+    int *s_a = reinterpret_cast<int *>(smem + kRecSlots * 16);
+    int *s_b = s_a + kMaxList;
+    uint32_t *s_tab = smem + kFastSlots * 16;
+    if (BWD) {
+        bool emit_all = p.fallback_all != 0;
+        if (!emit_all) {
+            const uint32_t flags = p.pl_count[(size_t)p.N * p.K] & ~kFlagBwdPrecise;
+            if (flags == 0u) return;
+            emit_all = (flags & kFlagGlobal) != 0u;
+        }
+        for (int b = blockIdx.x; b < p.total_packets; b += gridDim.x) {
+            march_packet<BWD, FADE8, false, TS, false, false, true>(p, b, s_a, s_b, s_rec, s_tab, emit_all, da);
+            __syncthreads();
+        }
+    } else {
+        march_packet<BWD, FADE8, false, TS, false, false, true>(p, blockIdx.x, s_a, s_b, s_rec, s_tab, true, da);
     }
 }
 

@@ -164,9 +164,11 @@ def build_accel(primtransfin, algo, fixedorder=False):
     return None, None, nodeaabb
 
 
-def _forward_impl(ctx, rays, cams, stepsize, primpos, primrot, primscale, template, warp, gradmode, options):
+def _forward_impl(ctx, rays, cams, stepsize, primpos, primrot, primscale, template, warp, gradmode, options, depth=False):
     """Shared body of MVPRaymarch.forward (rays = (raypos, raydir, tminmax)) and MVPRaymarchFromCameras.forward
-    (cams = (campos, camrot, focal, princpt, pixelcoords-or-(W,H), volradius): the rays are made inside the march)."""
+    (cams = (campos, camrot, focal, princpt, pixelcoords-or-(W,H), volradius): the rays are made inside the march).
+    depth=True (MVPRaymarchDepth, rays as tensors, algo 0): also the expected depth raydepth [N,H,W]; returns
+    (rayrgba, raydepth)."""
     algo = options["algo"]
     usebvh = options["usebvh"]
     if algo not in (0, 1):
@@ -229,13 +231,22 @@ def _forward_impl(ctx, rays, cams, stepsize, primpos, primrot, primscale, templa
     _, _, nodeaabb = build_accel((primpos, primrot, primscale), algo, fixedorder=True)
 
     rayrgba = torch.empty((N, H, W, 4), device=dev, dtype=torch.float32)
+    raydepth = torch.empty((N, H, W), device=dev, dtype=torch.float32) if depth else None
     raysat = rayaux = pl_count = pl_list = None
     pl_cap = 0
     if gradmode:
         raysat = torch.empty((N, H, W, 3), device=dev, dtype=torch.float32)
         rayaux, pl_count, pl_list, pl_cap = alloc_handoff(N, H, W, K, dev)
+        if depth and rayaux is None:  # (every owner of the depth backward reads the saturating sample's step from rayaux)
+            rayaux = torch.empty((N, H, W, 4), device=dev, dtype=torch.int32)
     with torch.cuda.device(dev), _hooks.timed("march_forward", dev):
-        if cams is None:
+        if depth:
+            _lib.check(_lib.get_lib().mvp_march_forward_depth(
+                N, H, W, K, ptr(raypos), ptr(raydir), float(stepsize), ptr(tminmax), ptr(nodeaabb), ptr(primpos),
+                ptr(primrot), ptr(primscale), TD, TH, TW, ptr(template), WD, WH, WW, ptr(warp), ptr(rayrgba),
+                ptr(raysat), ptr(rayaux), ptr(pl_count), ptr(pl_list), pl_cap, fadescale, fadeexp, ptr(_hooks.diag),
+                stream_ptr(dev), ptr(raydepth)), "mvp_march_forward_depth")
+        elif cams is None:
             _lib.check(_lib.get_lib().mvp_march_forward(
                 N, H, W, K, ptr(raypos), ptr(raydir), float(stepsize), ptr(tminmax), ptr(nodeaabb), ptr(primpos),
                 ptr(primrot), ptr(primscale), TD, TH, TW, ptr(template), WD, WH, WW, ptr(warp), ptr(rayrgba),
@@ -262,16 +273,16 @@ def _forward_impl(ctx, rays, cams, stepsize, primpos, primrot, primscale, templa
         _hooks.last_handoff_shape = (N, H, W, K, pl_cap)
     # (camera form in grad mode: raypos / raydir / tminmax are the tensors the forward march has just written)
     ctx.save_for_backward(raypos, raydir, tminmax, nodeaabb, primpos, primrot, primscale, template, raysat, rayaux,
-                          pl_count, pl_list, warp)
+                          pl_count, pl_list, warp, raydepth)
     ctx.pl_cap = pl_cap
     ctx.options = options
     ctx.stepsize = float(stepsize)
-    return rayrgba
+    return (rayrgba, raydepth) if depth else rayrgba
 
 
-def _backward_impl(ctx, grad_rayrgba):
+def _backward_impl(ctx, grad_rayrgba, grad_raydepth=None):
     (raypos, raydir, tminmax, nodeaabb, primpos, primrot, primscale, template, raysat, rayaux, pl_count,
-     pl_list, warp) = ctx.saved_tensors
+     pl_list, warp, raydepth) = ctx.saved_tensors
     if raysat is None:
         raise RuntimeError("backward through mvpraymarch needs grad mode enabled during the forward call")
     fadescale, fadeexp = float(ctx.options["fadescale"]), float(ctx.options["fadeexp"])
@@ -289,6 +300,16 @@ def _backward_impl(ctx, grad_rayrgba):
     grad_template = torch.empty_like(template)
     grad_warp = torch.empty_like(warp) if warp is not None else None
     WD, WH, WW = (warp.size(2), warp.size(3), warp.size(4)) if warp is not None else (0, 0, 0)
+    if raydepth is not None:  # (MVPRaymarchDepth)
+        grad_raydepth = (torch.zeros_like(raydepth) if grad_raydepth is None else grad_raydepth.contiguous().float())
+        with torch.cuda.device(dev), _hooks.timed("march_backward", dev):
+            _lib.check(_lib.get_lib().mvp_march_backward_depth(
+                N, H, W, K, ptr(raypos), ptr(raydir), ctx.stepsize, ptr(tminmax), ptr(nodeaabb), ptr(primpos),
+                ptr(primrot), ptr(primscale), TD, TH, TW, ptr(template), WD, WH, WW, ptr(warp), ptr(raysat),
+                ptr(rayaux), ptr(pl_count), ptr(pl_list), ctx.pl_cap, ptr(grad_rayrgba), ptr(grad_primpos),
+                ptr(grad_primrot), ptr(grad_primscale), ptr(grad_template), ptr(grad_warp), fadescale, fadeexp,
+                ptr(_hooks.diag), stream_ptr(dev), ptr(raydepth), ptr(grad_raydepth)), "mvp_march_backward_depth")
+        return grad_primpos, grad_primrot, grad_primscale, grad_template, grad_warp
     with torch.cuda.device(dev), _hooks.timed("march_backward", dev):
         _lib.check(_lib.get_lib().mvp_march_backward(
             N, H, W, K, ptr(raypos), ptr(raydir), ctx.stepsize, ptr(tminmax), ptr(nodeaabb), ptr(primpos),
@@ -331,6 +352,22 @@ class MVPRaymarchFromCameras(Function):
     def backward(ctx, grad_rayrgba):
         gp, gr, gs, gt, _ = _backward_impl(ctx, grad_rayrgba)
         return (None, None, None, None, None, None, None, gp, gr, gs, gt, None, None)
+
+
+class MVPRaymarchDepth(Function):
+    """MVPRaymarch with the expected-depth channel (mvp_march_forward_depth / mvp_march_backward_depth): returns
+    (rayrgba [N,H,W,4], raydepth [N,H,W]); gradients flow from both.  algo 0 only."""
+
+    @staticmethod
+    def forward(ctx, raypos, raydir, stepsize, tminmax, primpos, primrot, primscale, template, rayterm, gradmode,
+                options):
+        return _forward_impl(ctx, (raypos, raydir, tminmax), None, stepsize, primpos, primrot, primscale, template,
+                             None, gradmode, options, depth=True)
+
+    @staticmethod
+    def backward(ctx, grad_rayrgba, grad_raydepth):
+        gp, gr, gs, gt, _ = _backward_impl(ctx, grad_rayrgba, grad_raydepth)
+        return (None, None, None, None, gp, gr, gs, gt, None, None, None)
 
 
 _DEFAULT_OPTIONS = {"algo": 0, "usebvh": "fixedorder", "sortprims": False, "randomorder": False, "maxhitboxes": 512,
@@ -435,3 +472,61 @@ def mvpraymarch(
         },
     )
     return out
+
+
+def mvpraymarch_depth(
+    raypos,
+    raydir,
+    stepsize,
+    tminmax,
+    primtransf,
+    template,
+    warp,
+    rayterm=None,
+    algo=0,
+    usebvh="fixedorder",
+    sortprims=False,
+    randomorder=False,
+    maxhitboxes=512,
+    synchitboxes=True,
+    chlast=True,
+    fadescale=8.0,
+    fadeexp=8.0,
+    accum=0,
+    termthresh=0.0,
+    griddim=3,
+    blocksize=(8, 16),
+    bwdblocksize=(8, 16),
+):
+    """mvpraymarch(...) that also returns the expected termination depth: (rayrgba [N,H,W,4], raydepth [N,H,W]), both
+    differentiable.  raydepth = sum over the ray's samples of contrib_i * t_i (contrib_i: the sample's increment of alpha;
+    t_i: its lattice t), premultiplied by alpha like the colour and 0 where the ray hits nothing; the surface position image is
+    raypos * alpha + raydir * raydepth (Raymarcher.forward(with_pos_img=True)).  Same arguments and options as mvpraymarch.
+    Refused before any device work (NotImplementedError): algo=1 (the warp-field sampler) and fp16 slabs (mvpraymarch_half)."""
+    if algo != 0:
+        raise NotImplementedError("mvpraymarch_depth: only algo=0 (the slab sampler); the warp-field sampler has no depth "
+                                  "channel")
+    if torch.is_tensor(template) and template.dtype == torch.float16:
+        raise NotImplementedError("mvpraymarch_depth: fp32 slabs only (the fp16 path, mvpraymarch_half, has no depth channel)")
+    if isinstance(primtransf, tuple):
+        primpos, primrot, primscale = primtransf
+    else:  # packed layout, mvpraymarch.py:355-360
+        primpos, primrot, primscale = (
+            primtransf[:, :, 0, :].contiguous(),
+            primtransf[:, :, 1:4, :].contiguous(),
+            primtransf[:, :, 4, :].contiguous(),
+        )
+    if not chlast:
+        template = template.permute(0, 1, 3, 4, 5, 2).contiguous()
+    return MVPRaymarchDepth.apply(
+        raypos, raydir, stepsize, tminmax, primpos, primrot, primscale, template, rayterm, torch.is_grad_enabled(),
+        {"algo": algo, "usebvh": usebvh, "sortprims": sortprims, "randomorder": randomorder, "maxhitboxes": maxhitboxes,
+         "synchitboxes": synchitboxes, "chlast": True, "fadescale": fadescale, "fadeexp": fadeexp, "accum": accum,
+         "termthresh": termthresh, "griddim": griddim, "blocksize": blocksize, "bwdblocksize": bwdblocksize})
+
+
+def mvpraymarch_depth_from_cameras(*args, **kwargs):
+    """Not available: the fused camera entry point (mvpraymarch_from_cameras) does not materialise raypos / raydir, which
+    pos_img needs.  Make the rays with compute_raydirs and call mvpraymarch_depth."""
+    raise NotImplementedError("the expected-depth channel has no fused camera entry point: use compute_raydirs + "
+                              "mvpraymarch_depth")

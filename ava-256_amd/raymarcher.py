@@ -3,7 +3,8 @@
 API contract taken from the reference (models/raymarchers/mvpraymarcher.py:17-54): constructor
 `(volradius, dt=1.0)`, attributes `volume_radius` and `dt` (= dt / volradius, the march step in volume
 units), and `forward(raypos, raydir, tminmax, decout, renderoptions={}, rayterm=None, with_pos_img=None)`
-returning `(rayrgb [N,3,H,W], rayalpha [N,1,H,W], rayrgba [N,4,H,W] view, None)`.  The module owns no
+returning `(rayrgb [N,3,H,W], rayalpha [N,1,H,W], rayrgba [N,4,H,W] view, pos_img)`: pos_img is None unless
+`with_pos_img` is true, then [N,3,H,W] = raypos * alpha + raydir * raydepth (mvpraymarch_depth).  The module owns no
 parameters or buffers, so `state_dict()` keys of a model that embeds it are unchanged.
 """
 import inspect
@@ -14,7 +15,7 @@ from torch import nn
 
 from . import _lib
 from ._tensors import aligned, ptr, require_device_f32, stream_ptr
-from .mvpraymarch import mvpraymarch, mvpraymarch_from_cameras
+from .mvpraymarch import mvpraymarch, mvpraymarch_depth, mvpraymarch_from_cameras
 
 # renderoptions are forwarded only when they name a keyword of mvpraymarch (the reference filters with
 # mvpraymarch.__code__.co_varnames, mvpraymarcher.py:45; the parameter list is the same set of names)
@@ -67,6 +68,13 @@ class Raymarcher(nn.Module):
                 with_pos_img=None):
         opts = {k: v for k, v in (renderoptions or {}).items() if k in _OPTION_NAMES}
         prims = (decout["primpos"], decout["primrot"], decout["primscale"])
+        if with_pos_img:  # (the reference accepts the flag and returns None; models/autoencoder.py:246-251,279 asks for it)
+            rayrgba, raydepth = mvpraymarch_depth(raypos, raydir, self.dt, tminmax, prims, template=decout["template"],
+                                                  warp=decout.get("warp", None), rayterm=rayterm, **opts)
+            rayrgb, rayalpha, rayrgba_nchw = split_rgba_nchw(rayrgba)
+            # pos_img = sum_i contrib_i * (raypos + t_i * raydir), in the march's (volume-radius-normalised) units
+            pos_img = raypos.movedim(3, 1) * rayalpha + raydir.movedim(3, 1) * raydepth.unsqueeze(1)
+            return rayrgb, rayalpha, rayrgba_nchw, pos_img.contiguous()
         rayrgba = mvpraymarch(raypos, raydir, self.dt, tminmax, prims, template=decout["template"],
                               warp=decout.get("warp", None), rayterm=rayterm, **opts)
         rayrgb, rayalpha, rayrgba_nchw = split_rgba_nchw(rayrgba)

@@ -182,6 +182,30 @@ int mvp_march_backward_half(int N, int H, int W, int K, const float *raypos, con
                             const float *grad_rayrgba, float *grad_primpos, float *grad_primrot, float *grad_primscale,
                             float *grad_tplate, float fadescale, float fadeexp, uint32_t *diag, void *stream);
 
+/* The EXPECTED TERMINATION DEPTH (the reference's `with_pos_img`, which it never fills).  mvp_march_forward plus
+ * raydepth [N,H,W] = sum over the ray's samples of contrib_i * t_i, where contrib_i is the sample's increment of alpha (the
+ * saturating sample's clamped one included) and t_i = tmin + s_i * stepsize its lattice t: premultiplied by alpha like the
+ * colour, 0 where the ray hits nothing.  pos_img = raypos * alpha + raydir * raydepth.  fp32 slabs, no warp field (warp NULL,
+ * else MVP_ERR_BADARG).  rayrgba, raysat and the hand-off are bit for bit mvp_march_forward's. */
+int mvp_march_forward_depth(int N, int H, int W, int K, const float *raypos, const float *raydir, float stepsize,
+                            const float *tminmax, const float *nodeaabb, const float *primpos, const float *primrot,
+                            const float *primscale, int TD, int TH, int TW, const float *tplate, int WD, int WH, int WW,
+                            const float *warp, float *rayrgba, float *raysat, uint32_t *rayaux, uint32_t *primlist_count,
+                            uint32_t *primlist, int primlist_cap, float fadescale, float fadeexp, uint32_t *diag,
+                            void *stream, float *raydepth);
+/* Its backward: mvp_march_backward plus the upstream gradient grad_raydepth [N,H,W].  t behaves as a fifth channel whose sample
+ * value does not depend on the slab: every sample's opacity gradient gains stepsize * (t_i - t_sat) * grad_raydepth (t_sat = the
+ * t of the sample that saturated the ray, 0 if none), nothing reaches the template's RGB.  rayaux is REQUIRED (the saturating
+ * sample's step is read from it); warp / grad_warp must be NULL.  raydepth is the forward's output (validated, not read). */
+int mvp_march_backward_depth(int N, int H, int W, int K, const float *raypos, const float *raydir, float stepsize,
+                             const float *tminmax, const float *nodeaabb, const float *primpos, const float *primrot,
+                             const float *primscale, int TD, int TH, int TW, const float *tplate, int WD, int WH, int WW,
+                             const float *warp, const float *raysat, const uint32_t *rayaux, uint32_t *primlist_count,
+                             const uint32_t *primlist, int primlist_cap, const float *grad_rayrgba, float *grad_primpos,
+                             float *grad_primrot, float *grad_primscale, float *grad_tplate, float *grad_warp,
+                             float fadescale, float fadeexp, uint32_t *diag, void *stream, const float *raydepth,
+                             const float *grad_raydepth);
+
 /* The decode tail and its image loss in one pass each way: colour calibration `w * image + b`
  * (models/colorcals/colorcal.py:28-31, models/autoencoder.py:254-256), matting `rayrgb + (1 - rayalpha) * bg`
  * (autoencoder.py:263-265) and sum |irgbrec - image| (losses.py:12-14, ddp-train.py:404-405), read from / written to the
