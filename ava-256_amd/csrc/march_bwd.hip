@@ -1317,26 +1317,53 @@ __global__ __launch_bounds__(kPreciseWaves * 64, 2) void bwd_prim_precise_depth_
 
 }  // namespace mvp
 
-// hslab: tplate points at fp16 RGBA slabs (mvp_march_backward_half: 8^3, no warp field)
-static int march_backward_impl(int N, int H, int W, int K, const float *raypos, const float *raydir, float stepsize,
-                               const float *tminmax, const float *nodeaabb, const float *primpos, const float *primrot,
+// LDS bytes of a primitive-centric workgroup of `waves` waves: float4 slab + [2][Vp] int64 + ray queue + reduce area + length
+// buckets + list indices by rank (2 bytes per list slot; used by primitives whose list needs more than one round).  With a
+// warp field, + the warp grid (float4 per node) and its accumulators: [VWp] int64 (x | y) + [VWp] int32 z, from
+// p.prim_lds_base (set here).
+static size_t bwd_prim_lds_bytes(mvp::MarchParams &p, int waves, int primlist_cap) {
+    using namespace mvp;
+    const size_t padz = p.warp ? 0 : kGradPadZ;  // (bwd_prim_body: kPadZ)
+    const size_t V = (size_t)p.TD * p.TH * p.TW, Vp = (size_t)p.TD * ((size_t)p.TH * p.TW + padz);
+    size_t lds = V * 16 + Vp * 16 + (size_t)prim_queue_cap(waves) * 8 + 64 * sizeof(float) + 16 + kLenBuckets * 4 +
+                 (((size_t)(primlist_cap > 0 ? primlist_cap : 0) * 2 + 15) & ~(size_t)15);
+    if (p.warp) {
+        lds = (lds + 15) & ~(size_t)15;
+        p.prim_lds_base = (int)lds;
+        const size_t VW = (size_t)p.WD * p.WH * p.WW, VWp = (size_t)p.WD * ((size_t)p.WH * p.WW + padz);
+        lds += VW * 16 + VWp * 12;
+    }
+    return lds;
+}
+
+static int march_backward_impl(mvp::MarchVariant v, int N, int H, int W, int K, const float *raypos, const float *raydir,
+                               float stepsize, const float *tminmax, const float *nodeaabb, const float *primpos, const float *primrot,
                                const float *primscale, int TD, int TH, int TW, const float *tplate, int WD, int WH, int WW,
                                const float *warp, const float *raysat, const uint32_t *rayaux, uint32_t *primlist_count,
                                const uint32_t *primlist, int primlist_cap, const float *grad_rayrgba, float *grad_primpos,
                                float *grad_primrot, float *grad_primscale, float *grad_tplate, float *grad_warp,
-                               float fadescale, float fadeexp, uint32_t *diag, void *stream, bool hslab,
+                               float fadescale, float fadeexp, uint32_t *diag, void *stream,
                                const float *grad_raydepth = nullptr) {
     using namespace mvp;
     MarchParams p = {};
-    if (hslab && (warp || grad_warp)) return MVP_ERR_BADARG;
-    // depth (mvp_march_backward_depth): fp32 slabs, no warp field, and the forward's rayaux (every owner reads the saturating
-    // sample's step from it)
-    const bool depth = grad_raydepth != nullptr;
-    if (depth && (hslab || warp || grad_warp)) return MVP_ERR_BADARG;
-    if (depth && (long long)N * H * W > 0 && (!rayaux || !aligned16(rayaux))) return MVP_ERR_BADARG;
+    switch (v) {
+    case MarchVariant::kFp32:
+        break;
+    case MarchVariant::kTrainHalf:  // tplate points at fp16 RGBA slabs: 8^3, no warp field
+        if (warp || grad_warp) return MVP_ERR_BADARG;
+        if (K > 0 && (TD != 8 || TH != 8 || TW != 8 || (unsigned long long)K * 4096ull >= (1ull << 32)))
+            return MVP_ERR_UNSUPPORTED;
+        break;
+    case MarchVariant::kDepth:  // fp32 slabs, no warp field, and the forward's rayaux (every owner reads the saturating
+                                // sample's step from it)
+        if (!grad_raydepth || warp || grad_warp) return MVP_ERR_BADARG;
+        if ((long long)N * H * W > 0 && (!rayaux || !aligned16(rayaux))) return MVP_ERR_BADARG;
+        break;
+    case MarchVariant::kRenderHalf:  // forward only
+        return MVP_ERR_BADARG;
+    }
+    const bool hslab = v == MarchVariant::kTrainHalf, depth = v == MarchVariant::kDepth;
     const DepthArgs da = {nullptr, grad_raydepth};
-    if (hslab && K > 0 && (TD != 8 || TH != 8 || TW != 8 || (unsigned long long)K * 4096ull >= (1ull << 32)))
-        return MVP_ERR_UNSUPPORTED;
     p.N = N, p.H = H, p.W = W, p.K = K, p.TD = TD, p.TH = TH, p.TW = TW;
     p.WD = WD, p.WH = WH, p.WW = WW, p.warp = warp, p.grad_warp = grad_warp;
     if (warp && (WD < 2 || WH < 2 || WW < 2)) return MVP_ERR_UNSUPPORTED;
@@ -1359,20 +1386,9 @@ static int march_backward_impl(int N, int H, int W, int K, const float *raypos, 
     const size_t V = (size_t)TD * TH * TW;
     const bool norays = (long long)N * H * W == 0;
     if (!norays && (!raysat || !grad_rayrgba || !aligned16(grad_rayrgba))) return MVP_ERR_BADARG;
-    const size_t padz = warp ? 0 : kGradPadZ;  // (bwd_prim_body: kPadZ)
-    const size_t Vp = (size_t)TD * ((size_t)TH * TW + padz);
-    // float4 slab + [2][Vp] int64 + ray queue + reduce area + length buckets
     // 2 or 3 waves per workgroup by the work a primitive has: ray packets per primitive (see the note at kEntriesPerWave)
     const int pw = ((long long)p.tiles_x * p.tiles_y * 4 > 5ll * K) ? 3 : 2;
-    // + list indices by rank (2 bytes per list slot; used by primitives whose list needs more than one round)
-    size_t lds = V * 16 + Vp * 16 + (size_t)prim_queue_cap(pw) * 8 + 64 * sizeof(float) + 16 + kLenBuckets * 4 +
-                 (((size_t)(primlist_cap > 0 ? primlist_cap : 0) * 2 + 15) & ~(size_t)15);
-    if (warp) {  // + the warp grid (float4 per node) and its accumulators: [VWp] int64 (x | y) + [VWp] int32 z
-        lds = (lds + 15) & ~(size_t)15;
-        p.prim_lds_base = (int)lds;
-        const size_t VW = (size_t)WD * WH * WW, VWp = (size_t)WD * ((size_t)WH * WW + padz);
-        lds += VW * 16 + VWp * 12;
-    }
+    size_t lds = bwd_prim_lds_bytes(p, pw, primlist_cap);
 #ifdef MVP_DEBUG_HOOKS
     if (const char *e = getenv("MVP_DEBUG_LDS_PAD")) lds += (size_t)atoi(e);  // occupancy experiments: fewer workgroups per CU
 #endif
@@ -1460,15 +1476,8 @@ static int march_backward_impl(int N, int H, int W, int K, const float *raypos, 
         if (rc != MVP_OK) return rc;
         {  // the two-pass instantiation for the primitives that kernel marked (heavy-tailed upstream gradients); exits at
            // once otherwise.  Same LDS layout with kPreciseWaves waves per workgroup.
-            size_t lds2 = V * 16 + Vp * 16 + (size_t)prim_queue_cap(kPreciseWaves) * 8 + 64 * sizeof(float) + 16 + kLenBuckets * 4 +
-                          (((size_t)primlist_cap * 2 + 15) & ~(size_t)15);
             MarchParams p2 = p;
-            if (warp) {
-                lds2 = (lds2 + 15) & ~(size_t)15;
-                p2.prim_lds_base = (int)lds2;
-                const size_t VW = (size_t)WD * WH * WW, VWp = (size_t)WD * ((size_t)WH * WW + padz);
-                lds2 += VW * 16 + VWp * 12;
-            }
+            const size_t lds2 = bwd_prim_lds_bytes(p2, kPreciseWaves, primlist_cap);
             const dim3 g2((unsigned)(pb < 2048 ? pb : 2048)), b2(kPreciseWaves * 64);
             if (depth && fade8)
                 hipLaunchKernelGGL((bwd_prim_precise_depth_kernel<true>), g2, b2, lds2, st, p2, (int)pb, da);
@@ -1528,10 +1537,10 @@ extern "C" int mvp_march_backward(int N, int H, int W, int K, const float *raypo
                                   float *grad_primpos, float *grad_primrot, float *grad_primscale,
                                   float *grad_tplate, float *grad_warp, float fadescale, float fadeexp,
                                   uint32_t *diag, void *stream) {
-    return march_backward_impl(N, H, W, K, raypos, raydir, stepsize, tminmax, nodeaabb, primpos, primrot, primscale, TD, TH,
-                               TW, tplate, WD, WH, WW, warp, raysat, rayaux, primlist_count, primlist, primlist_cap,
-                               grad_rayrgba, grad_primpos, grad_primrot, grad_primscale, grad_tplate, grad_warp, fadescale,
-                               fadeexp, diag, stream, false);
+    return march_backward_impl(mvp::MarchVariant::kFp32, N, H, W, K, raypos, raydir, stepsize, tminmax, nodeaabb, primpos,
+                               primrot, primscale, TD, TH, TW, tplate, WD, WH, WW, warp, raysat, rayaux, primlist_count,
+                               primlist, primlist_cap, grad_rayrgba, grad_primpos, grad_primrot, grad_primscale, grad_tplate,
+                               grad_warp, fadescale, fadeexp, diag, stream);
 }
 
 // The backward over fp16 slabs (tplate_half [N,K,8,8,8,4] fp16, the slabs the forward marched): the same owners and hand-off
@@ -1544,10 +1553,11 @@ extern "C" int mvp_march_backward_half(int N, int H, int W, int K, const float *
                                        int primlist_cap, const float *grad_rayrgba, float *grad_primpos,
                                        float *grad_primrot, float *grad_primscale, float *grad_tplate, float fadescale,
                                        float fadeexp, uint32_t *diag, void *stream) {
-    return march_backward_impl(N, H, W, K, raypos, raydir, stepsize, tminmax, nodeaabb, primpos, primrot, primscale, TD, TH,
-                               TW, reinterpret_cast<const float *>(tplate_half), 0, 0, 0, nullptr, raysat, rayaux,
-                               primlist_count, primlist, primlist_cap, grad_rayrgba, grad_primpos, grad_primrot,
-                               grad_primscale, grad_tplate, nullptr, fadescale, fadeexp, diag, stream, true);
+    return march_backward_impl(mvp::MarchVariant::kTrainHalf, N, H, W, K, raypos, raydir, stepsize, tminmax, nodeaabb,
+                               primpos, primrot, primscale, TD, TH, TW, reinterpret_cast<const float *>(tplate_half), 0, 0,
+                               0, nullptr, raysat, rayaux, primlist_count, primlist, primlist_cap, grad_rayrgba,
+                               grad_primpos, grad_primrot, grad_primscale, grad_tplate, nullptr, fadescale, fadeexp, diag,
+                               stream);
 }
 
 // mvp_march_backward with the expected-depth channel of mvp_march_forward_depth: grad_raydepth [N,H,W] is the upstream gradient of
@@ -1563,10 +1573,9 @@ extern "C" int mvp_march_backward_depth(int N, int H, int W, int K, const float 
                                         float *grad_primpos, float *grad_primrot, float *grad_primscale,
                                         float *grad_tplate, float *grad_warp, float fadescale, float fadeexp,
                                         uint32_t *diag, void *stream, const float *raydepth, const float *grad_raydepth) {
-    if ((long long)N * H * W > 0 && (!raydepth || !grad_raydepth)) return MVP_ERR_BADARG;
-    if (!grad_raydepth) return MVP_ERR_BADARG;
-    return march_backward_impl(N, H, W, K, raypos, raydir, stepsize, tminmax, nodeaabb, primpos, primrot, primscale, TD, TH,
-                               TW, tplate, WD, WH, WW, warp, raysat, rayaux, primlist_count, primlist, primlist_cap,
-                               grad_rayrgba, grad_primpos, grad_primrot, grad_primscale, grad_tplate, grad_warp, fadescale,
-                               fadeexp, diag, stream, false, grad_raydepth);
+    if ((long long)N * H * W > 0 && !raydepth) return MVP_ERR_BADARG;
+    return march_backward_impl(mvp::MarchVariant::kDepth, N, H, W, K, raypos, raydir, stepsize, tminmax, nodeaabb, primpos,
+                               primrot, primscale, TD, TH, TW, tplate, WD, WH, WW, warp, raysat, rayaux, primlist_count,
+                               primlist, primlist_cap, grad_rayrgba, grad_primpos, grad_primrot, grad_primscale, grad_tplate,
+                               grad_warp, fadescale, fadeexp, diag, stream, grad_raydepth);
 }

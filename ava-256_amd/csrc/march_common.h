@@ -112,6 +112,14 @@ struct DepthArgs {
     float *raydepth;              // forward output
     const float *grad_raydepth;   // backward input
 };
+// Which march a C entry point runs (march_forward_impl in march_fwd.hip, march_backward_impl in march_bwd.hip): each extern
+// "C" wrapper names its variant, and the impl checks that variant's refusals in one place.
+enum class MarchVariant {
+    kFp32,        // fp32 slabs, optional warp field (mvp_march_forward, _cams, mvp_march_backward)
+    kRenderHalf,  // fp16 slabs, forward only, nothing handed to a backward (mvp_march_render_half)
+    kTrainHalf,   // fp16 slabs with the full hand-off (mvp_march_forward_half, _cams_half, mvp_march_backward_half)
+    kDepth,       // fp32 slabs with the expected-depth channel (mvp_march_forward_depth, mvp_march_backward_depth)
+};
 #ifdef MVP_DEBUG_HOOKS
 #define MVP_DEBUG_STAGE(P_) ((P_).debug_stage)
 #define MVP_DEBUG_FORCE_DFS(P_) ((P_).debug_force_dfs != 0)

@@ -11,26 +11,31 @@ struct CameraArgs {  // mvp_march_forward_cams: rays are made inside the march
     float *raypos_out, *raydir_out, *tminmax_out;  // all three or none
 };
 
-static int march_forward_impl(int N, int H, int W, int K, const float *raypos, const float *raydir, const CameraArgs *cams,
-                              float stepsize, const float *tminmax, const float *nodeaabb, const float *primpos,
-                              const float *primrot, const float *primscale, int TD, int TH, int TW,
+static int march_forward_impl(mvp::MarchVariant v, int N, int H, int W, int K, const float *raypos, const float *raydir,
+                              const CameraArgs *cams, float stepsize, const float *tminmax, const float *nodeaabb,
+                              const float *primpos, const float *primrot, const float *primscale, int TD, int TH, int TW,
                               const float *tplate, int WD, int WH, int WW, const float *warp, float *rayrgba,
                               float *raysat, uint32_t *rayaux, uint32_t *primlist_count, uint32_t *primlist,
                               int primlist_cap, float fadescale, float fadeexp, uint32_t *diag, void *stream,
-                              bool half_slabs = false, bool hslab_train = false, float *raydepth = nullptr) {
+                              float *raydepth = nullptr) {
     using namespace mvp;
     MarchParams p = {};
-    if (raydepth) {  // the expected-depth channel (mvp_march_forward_depth): fp32 slabs, rays as tensors, no warp field
-        if (warp || cams || half_slabs || hslab_train) return MVP_ERR_BADARG;
-    }
-    if (hslab_train) {  // fp16 RGBA slabs with the hand-off to mvp_march_backward_half: 8^3 slabs, no warp field
+    switch (v) {
+    case MarchVariant::kFp32:
+        break;
+    case MarchVariant::kDepth:  // the expected-depth channel into raydepth: fp32 slabs, rays as tensors, no warp field
+        if (!raydepth || warp || cams) return MVP_ERR_BADARG;
+        break;
+    case MarchVariant::kTrainHalf:  // fp16 RGBA slabs with the hand-off to mvp_march_backward_half: 8^3 slabs, no warp field
         if (warp) return MVP_ERR_BADARG;
         if (K > 0 && (TD != 8 || TH != 8 || TW != 8 || (unsigned long long)K * 4096ull >= (1ull << 32)))
             return MVP_ERR_UNSUPPORTED;
-    }
-    if (half_slabs) {  // the opt-in render path over fp16 RGBA slabs: forward only, nothing handed to a backward, 8^3 slabs
+        break;
+    case MarchVariant::kRenderHalf:  // the opt-in render path over fp16 RGBA slabs: forward only, nothing handed to a
+                                     // backward, 8^3 slabs
         if (warp || raysat || rayaux || primlist_count || primlist) return MVP_ERR_BADARG;
         if (TD != 8 || TH != 8 || TW != 8 || (unsigned long long)K * 4096ull >= (1ull << 32)) return MVP_ERR_UNSUPPORTED;
+        break;
     }
     if (cams) {
         p.campos = cams->campos, p.camrot = cams->camrot, p.focal = cams->focal, p.princpt = cams->princpt;
@@ -85,17 +90,17 @@ static int march_forward_impl(int N, int H, int W, int K, const float *raypos, c
             hipLaunchKernelGGL((march_kernel<false, true, true>), grid, block, 0, st, p);
         else
             hipLaunchKernelGGL((march_kernel<false, false, true>), grid, block, 0, st, p);
-    } else if (half_slabs) {
+    } else if (v == MarchVariant::kRenderHalf) {
         if (fade8)
             hipLaunchKernelGGL((march_half_kernel<true>), grid, block, 0, st, p);
         else
             hipLaunchKernelGGL((march_half_kernel<false>), grid, block, 0, st, p);
-    } else if (hslab_train) {
+    } else if (v == MarchVariant::kTrainHalf) {
         if (fade8)
             hipLaunchKernelGGL((march_hslab_kernel<false, true>), grid, block, 0, st, p);
         else
             hipLaunchKernelGGL((march_hslab_kernel<false, false>), grid, block, 0, st, p);
-    } else if (raydepth) {
+    } else if (v == MarchVariant::kDepth) {
         const bool cube8 = TD == 8 && TH == 8 && TW == 8 && (unsigned long long)K * 8192ull < (1ull << 32);
         if (fade8 && cube8)
             hipLaunchKernelGGL((march_depth_kernel<false, true, 8>), grid, block, 0, st, p, da);
@@ -126,9 +131,9 @@ extern "C" int mvp_march_forward(int N, int H, int W, int K, const float *raypos
                                  const float *tplate, int WD, int WH, int WW, const float *warp, float *rayrgba,
                                  float *raysat, uint32_t *rayaux, uint32_t *primlist_count, uint32_t *primlist,
                                  int primlist_cap, float fadescale, float fadeexp, uint32_t *diag, void *stream) {
-    return march_forward_impl(N, H, W, K, raypos, raydir, nullptr, stepsize, tminmax, nodeaabb, primpos, primrot,
-                              primscale, TD, TH, TW, tplate, WD, WH, WW, warp, rayrgba, raysat, rayaux, primlist_count,
-                              primlist, primlist_cap, fadescale, fadeexp, diag, stream);
+    return march_forward_impl(mvp::MarchVariant::kFp32, N, H, W, K, raypos, raydir, nullptr, stepsize, tminmax, nodeaabb,
+                              primpos, primrot, primscale, TD, TH, TW, tplate, WD, WH, WW, warp, rayrgba, raysat, rayaux,
+                              primlist_count, primlist, primlist_cap, fadescale, fadeexp, diag, stream);
 }
 
 extern "C" int mvp_march_forward_cams(int N, int H, int W, int K, const float *campos, const float *camrot,
@@ -140,9 +145,9 @@ extern "C" int mvp_march_forward_cams(int N, int H, int W, int K, const float *c
                                       float *raypos_out, float *raydir_out, float *tminmax_out, float fadescale,
                                       float fadeexp, uint32_t *diag, void *stream) {
     const CameraArgs cams = {campos, camrot, focal, princpt, pixelcoords, volradius, raypos_out, raydir_out, tminmax_out};
-    return march_forward_impl(N, H, W, K, nullptr, nullptr, &cams, stepsize, nullptr, nodeaabb, primpos, primrot,
-                              primscale, TD, TH, TW, tplate, 0, 0, 0, nullptr, rayrgba, raysat, rayaux, primlist_count,
-                              primlist, primlist_cap, fadescale, fadeexp, diag, stream);
+    return march_forward_impl(mvp::MarchVariant::kFp32, N, H, W, K, nullptr, nullptr, &cams, stepsize, nullptr, nodeaabb,
+                              primpos, primrot, primscale, TD, TH, TW, tplate, 0, 0, 0, nullptr, rayrgba, raysat, rayaux,
+                              primlist_count, primlist, primlist_cap, fadescale, fadeexp, diag, stream);
 }
 
 // The opt-in render path: the forward march over HALF-PRECISION slabs (fp16 RGBA, 8 bytes per voxel; made by
@@ -160,13 +165,13 @@ extern "C" int mvp_march_render_half(int N, int H, int W, int K, const float *ra
     if (campos) {
         if (raypos || raydir || tminmax) return MVP_ERR_BADARG;
         const CameraArgs cams = {campos, camrot, focal, princpt, pixelcoords, volradius, nullptr, nullptr, nullptr};
-        return march_forward_impl(N, H, W, K, nullptr, nullptr, &cams, stepsize, nullptr, nodeaabb, primpos, primrot,
-                                  primscale, TD, TH, TW, tp, 0, 0, 0, nullptr, rayrgba, nullptr, nullptr, nullptr, nullptr, 0,
-                                  fadescale, fadeexp, diag, stream, true);
+        return march_forward_impl(mvp::MarchVariant::kRenderHalf, N, H, W, K, nullptr, nullptr, &cams, stepsize, nullptr,
+                                  nodeaabb, primpos, primrot, primscale, TD, TH, TW, tp, 0, 0, 0, nullptr, rayrgba, nullptr,
+                                  nullptr, nullptr, nullptr, 0, fadescale, fadeexp, diag, stream);
     }
-    return march_forward_impl(N, H, W, K, raypos, raydir, nullptr, stepsize, tminmax, nodeaabb, primpos, primrot, primscale,
-                              TD, TH, TW, tp, 0, 0, 0, nullptr, rayrgba, nullptr, nullptr, nullptr, nullptr, 0, fadescale,
-                              fadeexp, diag, stream, true);
+    return march_forward_impl(mvp::MarchVariant::kRenderHalf, N, H, W, K, raypos, raydir, nullptr, stepsize, tminmax,
+                              nodeaabb, primpos, primrot, primscale, TD, TH, TW, tp, 0, 0, 0, nullptr, rayrgba, nullptr,
+                              nullptr, nullptr, nullptr, 0, fadescale, fadeexp, diag, stream);
 }
 
 // The training path over HALF-PRECISION slabs: mvp_march_forward / mvp_march_forward_cams without the warp field, reading fp16
@@ -178,10 +183,10 @@ extern "C" int mvp_march_forward_half(int N, int H, int W, int K, const float *r
                                       const void *tplate_half, float *rayrgba, float *raysat, uint32_t *rayaux,
                                       uint32_t *primlist_count, uint32_t *primlist, int primlist_cap, float fadescale,
                                       float fadeexp, uint32_t *diag, void *stream) {
-    return march_forward_impl(N, H, W, K, raypos, raydir, nullptr, stepsize, tminmax, nodeaabb, primpos, primrot,
-                              primscale, TD, TH, TW, reinterpret_cast<const float *>(tplate_half), 0, 0, 0, nullptr, rayrgba,
-                              raysat, rayaux, primlist_count, primlist, primlist_cap, fadescale, fadeexp, diag, stream,
-                              false, true);
+    return march_forward_impl(mvp::MarchVariant::kTrainHalf, N, H, W, K, raypos, raydir, nullptr, stepsize, tminmax,
+                              nodeaabb, primpos, primrot, primscale, TD, TH, TW, reinterpret_cast<const float *>(tplate_half),
+                              0, 0, 0, nullptr, rayrgba, raysat, rayaux, primlist_count, primlist, primlist_cap, fadescale,
+                              fadeexp, diag, stream);
 }
 
 extern "C" int mvp_march_forward_cams_half(int N, int H, int W, int K, const float *campos, const float *camrot,
@@ -193,10 +198,10 @@ extern "C" int mvp_march_forward_cams_half(int N, int H, int W, int K, const flo
                                            float *raypos_out, float *raydir_out, float *tminmax_out, float fadescale,
                                            float fadeexp, uint32_t *diag, void *stream) {
     const CameraArgs cams = {campos, camrot, focal, princpt, pixelcoords, volradius, raypos_out, raydir_out, tminmax_out};
-    return march_forward_impl(N, H, W, K, nullptr, nullptr, &cams, stepsize, nullptr, nodeaabb, primpos, primrot,
-                              primscale, TD, TH, TW, reinterpret_cast<const float *>(tplate_half), 0, 0, 0, nullptr, rayrgba,
-                              raysat, rayaux, primlist_count, primlist, primlist_cap, fadescale, fadeexp, diag, stream,
-                              false, true);
+    return march_forward_impl(mvp::MarchVariant::kTrainHalf, N, H, W, K, nullptr, nullptr, &cams, stepsize, nullptr,
+                              nodeaabb, primpos, primrot, primscale, TD, TH, TW, reinterpret_cast<const float *>(tplate_half),
+                              0, 0, 0, nullptr, rayrgba, raysat, rayaux, primlist_count, primlist, primlist_cap, fadescale,
+                              fadeexp, diag, stream);
 }
 
 // mvp_march_forward with the expected-depth channel: raydepth [N,H,W] = sum over the ray's samples of contrib * t (premultiplied
@@ -209,8 +214,7 @@ extern "C" int mvp_march_forward_depth(int N, int H, int W, int K, const float *
                                        float *raysat, uint32_t *rayaux, uint32_t *primlist_count, uint32_t *primlist,
                                        int primlist_cap, float fadescale, float fadeexp, uint32_t *diag, void *stream,
                                        float *raydepth) {
-    if (!raydepth || warp) return MVP_ERR_BADARG;
-    return march_forward_impl(N, H, W, K, raypos, raydir, nullptr, stepsize, tminmax, nodeaabb, primpos, primrot,
-                              primscale, TD, TH, TW, tplate, WD, WH, WW, warp, rayrgba, raysat, rayaux, primlist_count,
-                              primlist, primlist_cap, fadescale, fadeexp, diag, stream, false, false, raydepth);
+    return march_forward_impl(mvp::MarchVariant::kDepth, N, H, W, K, raypos, raydir, nullptr, stepsize, tminmax, nodeaabb,
+                              primpos, primrot, primscale, TD, TH, TW, tplate, WD, WH, WW, warp, rayrgba, raysat, rayaux,
+                              primlist_count, primlist, primlist_cap, fadescale, fadeexp, diag, stream, raydepth);
 }

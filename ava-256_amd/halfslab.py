@@ -23,20 +23,14 @@ The fp16 rounding is a straight-through step: the rays march over template_half 
 tensors -- are the march's gradients at the rounded slab values.  The differentiable slab input is the fp32 master: autograd
 casts a gradient to its input's dtype, and fp16 slab gradients would underflow.  Bit for bit what mvpraymarch gives on
 template_half.float() (tests/test_gpu_half_train.py).  No warp field, 8^3 slabs."""
-import importlib
 import math
 
 import torch
 
-from torch.autograd import Function
-
 from . import _hooks, _lib
 from ._tensors import aligned, ptr, require_device_f32, stream_ptr
-from .mvpraymarch import build_accel
-
-# the MODULE (the package re-exports a function of that name): alloc_handoff is looked up on it at call time, so that
-# _hooks.patched_handoff applies to this operator too
-_mvp = importlib.import_module(__package__ + ".mvpraymarch")
+from .mvpraymarch import (_DEFAULT_OPTIONS, _MVPRaymarchHalf, _MVPRaymarchHalfFromCameras, _camera_args,
+                          _unpack_primtransf, build_accel)
 
 
 def template_to_half(template):
@@ -67,12 +61,8 @@ def assemble_template_half(tex, opacity, nboxes, boxsize=8):
     return out
 
 
-def _prims(primtransf):
-    if isinstance(primtransf, tuple):
-        primpos, primrot, primscale = primtransf
-    else:  # packed [N,K,5,3] (mvpraymarch.py:355-360)
-        primpos, primrot, primscale = (primtransf[:, :, 0, :].contiguous(), primtransf[:, :, 1:4, :].contiguous(),
-                                       primtransf[:, :, 4, :].contiguous())
+def _device_prims(primtransf):
+    primpos, primrot, primscale = _unpack_primtransf(primtransf)
     return (require_device_f32("primpos", primpos), require_device_f32("primrot", primrot),
             require_device_f32("primscale", primscale))
 
@@ -112,7 +102,7 @@ def _no_grad(*tensors):
 
 def render_half(raypos, raydir, stepsize, tminmax, primtransf, template_half, fadescale=8.0, fadeexp=8.0):
     """mvpraymarch(...) without gradients over fp16 slabs -> rayrgba [N,H,W,4] float32."""
-    primpos, primrot, primscale = _prims(primtransf)
+    primpos, primrot, primscale = _device_prims(primtransf)
     _no_grad(raypos, raydir, tminmax, primpos, primrot, primscale, template_half)
     raypos = aligned(require_device_f32("raypos", raypos))
     raydir = aligned(require_device_f32("raydir", raydir))
@@ -138,19 +128,9 @@ def render_half(raypos, raydir, stepsize, tminmax, primtransf, template_half, fa
 def render_half_from_cameras(campos, camrot, focal, princpt, pixelcoords, volradius, stepsize, primtransf, template_half,
                              fadescale=8.0, fadeexp=8.0):
     """mvpraymarch_from_cameras(...) without gradients over fp16 slabs (rays made inside the march)."""
-    primpos, primrot, primscale = _prims(primtransf)
+    primpos, primrot, primscale = _device_prims(primtransf)
     _no_grad(campos, camrot, focal, princpt, primpos, primrot, primscale, template_half)
-    campos, camrot = require_device_f32("campos", campos), require_device_f32("camrot", camrot)
-    focal, princpt = require_device_f32("focal", focal), require_device_f32("princpt", princpt)
-    N = campos.size(0)
-    assert campos.shape == (N, 3) and camrot.shape == (N, 3, 3) and focal.shape == (N, 2) and princpt.shape == (N, 2)
-    if isinstance(pixelcoords, tuple):
-        W, H = pixelcoords
-        pc = None
-    else:
-        pc = aligned(require_device_f32("pixelcoords", pixelcoords))
-        assert pc.dim() == 4 and pc.size(0) == N and pc.size(3) == 2
-        H, W = pc.size(1), pc.size(2)
+    campos, camrot, focal, princpt, pc, N, H, W = _camera_args(campos, camrot, focal, princpt, pixelcoords)
     K = _check_prims(primpos, primrot, primscale, N)
     th = _check_half(template_half, N, K)
     _same_device(campos, camrot, focal, princpt, pc, primpos, primrot, primscale, th)
@@ -231,118 +211,9 @@ def _half_of(template, template_half):
     return aligned(template_half.detach())
 
 
-def _forward_half_impl(ctx, rays, cams, stepsize, primpos, primrot, primscale, template, template_half, gradmode,
-                       fadescale, fadeexp):
-    """mvpraymarch._forward_impl over fp16 slabs: the same hand-off allocation (mvpraymarch.alloc_handoff, looked up at call
-    time so that _hooks.patched_handoff applies), list-capacity feedback and test hooks."""
-    fadescale, fadeexp = float(fadescale), float(fadeexp)
-    primpos = require_device_f32("primpos", primpos)
-    primrot = require_device_f32("primrot", primrot)
-    primscale = require_device_f32("primscale", primscale)
-    template = require_device_f32("template", template)
-    if cams is None:
-        raypos, raydir, tminmax = (aligned(require_device_f32(n, t)) for n, t in zip(("raypos", "raydir", "tminmax"), rays))
-        N, H, W = raypos.size(0), raypos.size(1), raypos.size(2)
-    else:
-        campos, camrot, focal, princpt, pc, W, H, volradius = cams
-        N = campos.size(0)
-        raypos = raydir = tminmax = None
-    K = primpos.size(1)
-    th = _half_of(template, template_half)
-    dev = primpos.device
-    _, _, nodeaabb = build_accel((primpos, primrot, primscale), 0, fixedorder=True)
-
-    rayrgba = torch.empty((N, H, W, 4), device=dev, dtype=torch.float32)
-    raysat = rayaux = pl_count = pl_list = None
-    pl_cap = 0
-    if gradmode:
-        raysat = torch.empty((N, H, W, 3), device=dev, dtype=torch.float32)
-        rayaux, pl_count, pl_list, pl_cap = _mvp.alloc_handoff(N, H, W, K, dev)
-    lib = _lib.get_lib()
-    with torch.cuda.device(dev), _hooks.timed("march_forward_half", dev):
-        if cams is None:
-            _lib.check(lib.mvp_march_forward_half(
-                N, H, W, K, ptr(raypos), ptr(raydir), float(stepsize), ptr(tminmax), ptr(nodeaabb), ptr(primpos),
-                ptr(primrot), ptr(primscale), 8, 8, 8, ptr(th), ptr(rayrgba), ptr(raysat), ptr(rayaux), ptr(pl_count),
-                ptr(pl_list), pl_cap, fadescale, fadeexp, ptr(_hooks.diag), stream_ptr(dev)), "mvp_march_forward_half")
-        else:
-            if gradmode:  # the backward's ray tensors, written by the forward march itself
-                raypos = torch.empty((N, H, W, 3), device=dev, dtype=torch.float32)
-                raydir = torch.empty((N, H, W, 3), device=dev, dtype=torch.float32)
-                tminmax = torch.empty((N, H, W, 2), device=dev, dtype=torch.float32)
-            _lib.check(lib.mvp_march_forward_cams_half(
-                N, H, W, K, ptr(campos), ptr(camrot), ptr(focal), ptr(princpt), ptr(pc), float(volradius),
-                float(stepsize), ptr(nodeaabb), ptr(primpos), ptr(primrot), ptr(primscale), 8, 8, 8, ptr(th),
-                ptr(rayrgba), ptr(raysat), ptr(rayaux), ptr(pl_count), ptr(pl_list), pl_cap, ptr(raypos), ptr(raydir),
-                ptr(tminmax), fadescale, fadeexp, ptr(_hooks.diag), stream_ptr(dev)), "mvp_march_forward_cams_half")
-
-    if pl_count is not None:
-        with torch.cuda.device(dev):
-            _mvp.note_list_demand(pl_count, N, H, W, K)
-    if _hooks.keep_raysat:
-        _hooks.last_raysat = raysat
-        _hooks.last_pl_count = pl_count
-        _hooks.last_flags_index = N * K
-        _hooks.last_handoff_shape = (N, H, W, K, pl_cap)
-    ctx.save_for_backward(raypos, raydir, tminmax, nodeaabb, primpos, primrot, primscale, th, raysat, rayaux, pl_count,
-                          pl_list)
-    ctx.pl_cap, ctx.stepsize, ctx.fade = pl_cap, float(stepsize), (fadescale, fadeexp)
-    return rayrgba
-
-
-def _backward_half_impl(ctx, grad_rayrgba):
-    (raypos, raydir, tminmax, nodeaabb, primpos, primrot, primscale, th, raysat, rayaux, pl_count,
-     pl_list) = ctx.saved_tensors
-    if raysat is None:
-        raise RuntimeError("backward through mvpraymarch_half needs grad mode enabled during the forward call")
-    N, H, W = raypos.size(0), raypos.size(1), raypos.size(2)
-    K = primpos.size(1)
-    dev = raypos.device
-    grad_rayrgba = aligned(grad_rayrgba.contiguous().float())
-    # all four are overwritten by the library; the slab gradient is fp32, shaped like the fp32 master
-    grad_primpos = torch.empty_like(primpos)
-    grad_primrot = torch.empty_like(primrot)
-    grad_primscale = torch.empty_like(primscale)
-    grad_template = torch.empty(th.shape, device=dev, dtype=torch.float32)
-    with torch.cuda.device(dev), _hooks.timed("march_backward_half", dev):
-        _lib.check(_lib.get_lib().mvp_march_backward_half(
-            N, H, W, K, ptr(raypos), ptr(raydir), ctx.stepsize, ptr(tminmax), ptr(nodeaabb), ptr(primpos), ptr(primrot),
-            ptr(primscale), 8, 8, 8, ptr(th), ptr(raysat), ptr(rayaux), ptr(pl_count), ptr(pl_list), ctx.pl_cap,
-            ptr(grad_rayrgba), ptr(grad_primpos), ptr(grad_primrot), ptr(grad_primscale), ptr(grad_template),
-            ctx.fade[0], ctx.fade[1], ptr(_hooks.diag), stream_ptr(dev)), "mvp_march_backward_half")
-    return grad_primpos, grad_primrot, grad_primscale, grad_template
-
-
-class MVPRaymarchHalf(Function):
-    """MVPRaymarch over fp16 slabs (straight-through rounding; see the module docstring)."""
-
-    @staticmethod
-    def forward(ctx, raypos, raydir, stepsize, tminmax, primpos, primrot, primscale, template, template_half, gradmode,
-                fadescale, fadeexp):
-        return _forward_half_impl(ctx, (raypos, raydir, tminmax), None, stepsize, primpos, primrot, primscale, template,
-                                  template_half, gradmode, fadescale, fadeexp)
-
-    @staticmethod
-    def backward(ctx, grad_rayrgba):
-        gp, gr, gs, gt = _backward_half_impl(ctx, grad_rayrgba)
-        return None, None, None, None, gp, gr, gs, gt, None, None, None, None
-
-
-class MVPRaymarchHalfFromCameras(Function):
-    """MVPRaymarchFromCameras over fp16 slabs: rays made inside the march, written for the backward in grad mode."""
-
-    @staticmethod
-    def forward(ctx, campos, camrot, focal, princpt, pixelcoords, volradius, stepsize, primpos, primrot, primscale, template,
-                template_half, gradmode, fadescale, fadeexp, wh):
-        W, H = wh
-        cams = (campos, camrot, focal, princpt, pixelcoords, W, H, volradius)
-        return _forward_half_impl(ctx, None, cams, stepsize, primpos, primrot, primscale, template, template_half, gradmode,
-                                  fadescale, fadeexp)
-
-    @staticmethod
-    def backward(ctx, grad_rayrgba):
-        gp, gr, gs, gt = _backward_half_impl(ctx, grad_rayrgba)
-        return (None,) * 7 + (gp, gr, gs, gt) + (None,) * 5
+def _fade_options(fadescale, fadeexp):
+    """mvpraymarch's default options with the two this path takes."""
+    return dict(_DEFAULT_OPTIONS, fadescale=fadescale, fadeexp=fadeexp)
 
 
 def mvpraymarch_half(raypos, raydir, stepsize, tminmax, primtransf, template, template_half=None, fadescale=8.0,
@@ -350,7 +221,7 @@ def mvpraymarch_half(raypos, raydir, stepsize, tminmax, primtransf, template, te
     """mvpraymarch(...) over fp16 slabs, with gradients: template is the fp32 master [N,K,8,8,8,4]; template_half its
     round-to-nearest-even copy (float16, same shape; made here when None).  Returns rayrgba [N,H,W,4] float32.  `warp` /
     `algo` exist only to be refused (no warp-field sampler on this path)."""
-    primpos, primrot, primscale = _split_prims(primtransf)
+    primpos, primrot, primscale = _unpack_primtransf(primtransf)
     for name, t in (("raypos", raypos), ("raydir", raydir), ("tminmax", tminmax)):
         if not torch.is_tensor(t):
             raise TypeError("%s must be a tensor" % name)
@@ -359,15 +230,15 @@ def mvpraymarch_half(raypos, raydir, stepsize, tminmax, primtransf, template, te
         raise ValueError("raypos / raydir / tminmax must be [N,H,W,3] / [N,H,W,3] / [N,H,W,2]")
     _check_train_half_args(raypos.size(0), primpos, primrot, primscale, template, template_half, warp, algo,
                            (raypos, raydir, tminmax))
-    return MVPRaymarchHalf.apply(raypos, raydir, stepsize, tminmax, primpos, primrot, primscale, template, template_half,
-                                 torch.is_grad_enabled(), fadescale, fadeexp)
+    return _MVPRaymarchHalf.apply(raypos, raydir, stepsize, tminmax, primpos, primrot, primscale, template, template_half,
+                                  torch.is_grad_enabled(), _fade_options(fadescale, fadeexp))
 
 
 def mvpraymarch_half_from_cameras(campos, camrot, focal, princpt, pixelcoords, volradius, stepsize, primtransf, template,
                                   template_half=None, fadescale=8.0, fadeexp=8.0, warp=None, algo=0):
     """mvpraymarch_from_cameras(...) over fp16 slabs, with gradients (see mvpraymarch_half).  pixelcoords: [N,H,W,2] tensor
     or a (W, H) tuple."""
-    primpos, primrot, primscale = _split_prims(primtransf)
+    primpos, primrot, primscale = _unpack_primtransf(primtransf)
     for name, t in (("campos", campos), ("camrot", camrot), ("focal", focal), ("princpt", princpt)):
         if not torch.is_tensor(t):
             raise TypeError("%s must be a tensor" % name)
@@ -376,26 +247,15 @@ def mvpraymarch_half_from_cameras(campos, camrot, focal, princpt, pixelcoords, v
         raise ValueError("campos / camrot / focal / princpt must be [N,3] / [N,3,3] / [N,2] / [N,2]")
     if isinstance(pixelcoords, tuple):
         W, H = pixelcoords
-        pc = None
-    else:
-        if not torch.is_tensor(pixelcoords) or pixelcoords.dim() != 4 or pixelcoords.size(0) != N or \
-                pixelcoords.size(3) != 2:
-            raise ValueError("pixelcoords must be [N,H,W,2] or a (W, H) tuple")
-        H, W = pixelcoords.size(1), pixelcoords.size(2)
-        pc = pixelcoords
+        pixelcoords = (int(W), int(H))
+    elif not torch.is_tensor(pixelcoords) or pixelcoords.dim() != 4 or pixelcoords.size(0) != N or pixelcoords.size(3) != 2:
+        raise ValueError("pixelcoords must be [N,H,W,2] or a (W, H) tuple")
     _check_train_half_args(N, primpos, primrot, primscale, template, template_half, warp, algo,
-                           (campos, camrot, focal, princpt, pc))
-    campos, camrot = require_device_f32("campos", campos), require_device_f32("camrot", camrot)
-    focal, princpt = require_device_f32("focal", focal), require_device_f32("princpt", princpt)
-    if pc is not None:
-        pc = aligned(require_device_f32("pixelcoords", pc))
-    return MVPRaymarchHalfFromCameras.apply(campos, camrot, focal, princpt, pc, float(volradius), stepsize, primpos,
-                                            primrot, primscale, template, template_half, torch.is_grad_enabled(),
-                                            fadescale, fadeexp, (int(W), int(H)))
-
-
-def _split_prims(primtransf):
-    if isinstance(primtransf, tuple):
-        return primtransf
-    return (primtransf[:, :, 0, :].contiguous(), primtransf[:, :, 1:4, :].contiguous(),
-            primtransf[:, :, 4, :].contiguous())
+                           (campos, camrot, focal, princpt, pixelcoords))
+    for name, t in (("campos", campos), ("camrot", camrot), ("focal", focal), ("princpt", princpt)):
+        require_device_f32(name, t)
+    if torch.is_tensor(pixelcoords):
+        require_device_f32("pixelcoords", pixelcoords)
+    return _MVPRaymarchHalfFromCameras.apply(campos, camrot, focal, princpt, pixelcoords, float(volradius), stepsize,
+                                             primpos, primrot, primscale, template, template_half,
+                                             torch.is_grad_enabled(), _fade_options(fadescale, fadeexp))

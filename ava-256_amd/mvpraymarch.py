@@ -164,11 +164,37 @@ def build_accel(primtransfin, algo, fixedorder=False):
     return None, None, nodeaabb
 
 
-def _forward_impl(ctx, rays, cams, stepsize, primpos, primrot, primscale, template, warp, gradmode, options, depth=False):
-    """Shared body of MVPRaymarch.forward (rays = (raypos, raydir, tminmax)) and MVPRaymarchFromCameras.forward
-    (cams = (campos, camrot, focal, princpt, pixelcoords-or-(W,H), volradius): the rays are made inside the march).
-    depth=True (MVPRaymarchDepth, rays as tensors, algo 0): also the expected depth raydepth [N,H,W]; returns
-    (rayrgba, raydepth)."""
+def _unpack_primtransf(primtransf):
+    """(primpos, primrot, primscale) from the tuple or the packed [N,K,5,3] layout (mvpraymarch.py:355-360)."""
+    if isinstance(primtransf, tuple):
+        return primtransf
+    return (primtransf[:, :, 0, :].contiguous(), primtransf[:, :, 1:4, :].contiguous(),
+            primtransf[:, :, 4, :].contiguous())
+
+
+def _camera_args(campos, camrot, focal, princpt, pixelcoords):
+    """The camera form's tensors on the device, pixelcoords a [N,H,W,2] tensor or a (W, H) tuple like compute_raydirs.
+    Returns (campos, camrot, focal, princpt, pixelcoords tensor or None, N, H, W)."""
+    campos, camrot = require_device_f32("campos", campos), require_device_f32("camrot", camrot)
+    focal, princpt = require_device_f32("focal", focal), require_device_f32("princpt", princpt)
+    N = campos.size(0)
+    if isinstance(pixelcoords, tuple):
+        (W, H), pc = pixelcoords, None
+    else:
+        pc = aligned(require_device_f32("pixelcoords", pixelcoords))
+        assert pc.dim() == 4 and pc.size(0) == N and pc.size(3) == 2
+        H, W = pc.size(1), pc.size(2)
+    assert campos.shape == (N, 3) and camrot.shape == (N, 3, 3) and focal.shape == (N, 2) and princpt.shape == (N, 2)
+    return campos, camrot, focal, princpt, pc, N, H, W
+
+
+def _forward_impl(ctx, rays, cams, stepsize, primpos, primrot, primscale, template, warp, gradmode, options, depth=False,
+                  half=False, template_half=None):
+    """The forward of every differentiable march.  Rays: rays = (raypos, raydir, tminmax), or cams = (campos, camrot, focal,
+    princpt, pixelcoords-or-(W,H), volradius) and the rays are made inside the march.  Slabs: the fp32 `template`, or
+    half=True: the fp16 slabs template_half (made from the fp32 master `template` when None; the gradient is still the fp32
+    master's).  depth=True: also the expected depth raydepth [N,H,W]; returns (rayrgba, raydepth).  The C entry point is
+    mvp_march_forward[_cams][_half][_depth]."""
     algo = options["algo"]
     usebvh = options["usebvh"]
     if algo not in (0, 1):
@@ -203,18 +229,8 @@ def _forward_impl(ctx, rays, cams, stepsize, primpos, primrot, primscale, templa
     else:
         if warp is not None:
             raise NotImplementedError("the fused camera entry point has no warp-field variant (algo 0 only)")
-        campos, camrot, focal, princpt, pixelcoords, volradius = cams
-        campos, camrot = require_device_f32("campos", campos), require_device_f32("camrot", camrot)
-        focal, princpt = require_device_f32("focal", focal), require_device_f32("princpt", princpt)
-        N = campos.size(0)
-        if isinstance(pixelcoords, tuple):
-            W, H = pixelcoords
-            pc = None
-        else:
-            pc = aligned(require_device_f32("pixelcoords", pixelcoords))
-            H, W = pc.size(1), pc.size(2)
-            assert pc.size(0) == N and pc.size(3) == 2
-        assert campos.shape == (N, 3) and camrot.shape == (N, 3, 3) and focal.shape == (N, 2) and princpt.shape == (N, 2)
+        campos, camrot, focal, princpt, pc, N, H, W = _camera_args(*cams[:5])
+        volradius = cams[5]
         raypos = raydir = tminmax = None
     K = primpos.size(1)
     assert primpos.shape == (N, K, 3) and primrot.shape == (N, K, 3, 3) and primscale.shape == (N, K, 3)
@@ -227,7 +243,11 @@ def _forward_impl(ctx, rays, cams, stepsize, primpos, primrot, primscale, templa
         assert warp.dim() == 6 and warp.size(-1) == 3 and warp.shape[:2] == (N, K)   # mvpraymarch.py:124
         WD, WH, WW = warp.size(2), warp.size(3), warp.size(4)
 
-    template = aligned(template)
+    if half:
+        from .halfslab import _half_of  # (halfslab imports this module)
+        slabs = _half_of(template, template_half)
+    else:
+        slabs = aligned(template)
     _, _, nodeaabb = build_accel((primpos, primrot, primscale), algo, fixedorder=True)
 
     rayrgba = torch.empty((N, H, W, 4), device=dev, dtype=torch.float32)
@@ -236,32 +256,28 @@ def _forward_impl(ctx, rays, cams, stepsize, primpos, primrot, primscale, templa
     pl_cap = 0
     if gradmode:
         raysat = torch.empty((N, H, W, 3), device=dev, dtype=torch.float32)
+        # (alloc_handoff is looked up at call time: _hooks.patched_handoff replaces it)
         rayaux, pl_count, pl_list, pl_cap = alloc_handoff(N, H, W, K, dev)
-        if depth and rayaux is None:  # (every owner of the depth backward reads the saturating sample's step from rayaux)
+        if depth and rayaux is None:  # _hooks.patched_handoff(ray_centric=True) hands off nothing, but every owner of
+            # the depth backward reads the saturating sample's step from rayaux
             rayaux = torch.empty((N, H, W, 4), device=dev, dtype=torch.int32)
-    with torch.cuda.device(dev), _hooks.timed("march_forward", dev):
-        if depth:
-            _lib.check(_lib.get_lib().mvp_march_forward_depth(
-                N, H, W, K, ptr(raypos), ptr(raydir), float(stepsize), ptr(tminmax), ptr(nodeaabb), ptr(primpos),
-                ptr(primrot), ptr(primscale), TD, TH, TW, ptr(template), WD, WH, WW, ptr(warp), ptr(rayrgba),
-                ptr(raysat), ptr(rayaux), ptr(pl_count), ptr(pl_list), pl_cap, fadescale, fadeexp, ptr(_hooks.diag),
-                stream_ptr(dev), ptr(raydepth)), "mvp_march_forward_depth")
-        elif cams is None:
-            _lib.check(_lib.get_lib().mvp_march_forward(
-                N, H, W, K, ptr(raypos), ptr(raydir), float(stepsize), ptr(tminmax), ptr(nodeaabb), ptr(primpos),
-                ptr(primrot), ptr(primscale), TD, TH, TW, ptr(template), WD, WH, WW, ptr(warp), ptr(rayrgba),
-                ptr(raysat), ptr(rayaux), ptr(pl_count), ptr(pl_list), pl_cap, fadescale, fadeexp, ptr(_hooks.diag),
-                stream_ptr(dev)), "mvp_march_forward")
+    name = "mvp_march_forward" + ("_cams" if cams is not None else "") + ("_half" if half else "") + \
+        ("_depth" if depth else "")
+    with torch.cuda.device(dev), _hooks.timed("march_forward_half" if half else "march_forward", dev):
+        handoff = (ptr(rayrgba), ptr(raysat), ptr(rayaux), ptr(pl_count), ptr(pl_list), pl_cap)
+        tail = (fadescale, fadeexp, ptr(_hooks.diag), stream_ptr(dev))
+        prims = (ptr(nodeaabb), ptr(primpos), ptr(primrot), ptr(primscale), TD, TH, TW, ptr(slabs))
+        if cams is None:
+            args = ((N, H, W, K, ptr(raypos), ptr(raydir), float(stepsize), ptr(tminmax)) + prims +
+                    (() if half else (WD, WH, WW, ptr(warp))) + handoff + tail + ((ptr(raydepth),) if depth else ()))
         else:
             if gradmode:  # the backward's ray tensors: written by the forward march itself (no raydirs launch)
                 raypos = torch.empty((N, H, W, 3), device=dev, dtype=torch.float32)
                 raydir = torch.empty((N, H, W, 3), device=dev, dtype=torch.float32)
                 tminmax = torch.empty((N, H, W, 2), device=dev, dtype=torch.float32)
-            _lib.check(_lib.get_lib().mvp_march_forward_cams(
-                N, H, W, K, ptr(campos), ptr(camrot), ptr(focal), ptr(princpt), ptr(pc), float(volradius),
-                float(stepsize), ptr(nodeaabb), ptr(primpos), ptr(primrot), ptr(primscale), TD, TH, TW, ptr(template),
-                ptr(rayrgba), ptr(raysat), ptr(rayaux), ptr(pl_count), ptr(pl_list), pl_cap, ptr(raypos), ptr(raydir),
-                ptr(tminmax), fadescale, fadeexp, ptr(_hooks.diag), stream_ptr(dev)), "mvp_march_forward_cams")
+            args = ((N, H, W, K, ptr(campos), ptr(camrot), ptr(focal), ptr(princpt), ptr(pc), float(volradius),
+                     float(stepsize)) + prims + handoff + (ptr(raypos), ptr(raydir), ptr(tminmax)) + tail)
+        _lib.check(getattr(_lib.get_lib(), name)(*args), name)
 
     if pl_count is not None:
         with torch.cuda.device(dev):
@@ -272,51 +288,50 @@ def _forward_impl(ctx, rays, cams, stepsize, primpos, primrot, primscale, templa
         _hooks.last_flags_index = N * K     # pl_count[N*K] = the flags word (include/mvp_abi.h)
         _hooks.last_handoff_shape = (N, H, W, K, pl_cap)
     # (camera form in grad mode: raypos / raydir / tminmax are the tensors the forward march has just written)
-    ctx.save_for_backward(raypos, raydir, tminmax, nodeaabb, primpos, primrot, primscale, template, raysat, rayaux,
+    ctx.save_for_backward(raypos, raydir, tminmax, nodeaabb, primpos, primrot, primscale, slabs, raysat, rayaux,
                           pl_count, pl_list, warp, raydepth)
     ctx.pl_cap = pl_cap
     ctx.options = options
     ctx.stepsize = float(stepsize)
+    ctx.half = half
     return (rayrgba, raydepth) if depth else rayrgba
 
 
 def _backward_impl(ctx, grad_rayrgba, grad_raydepth=None):
-    (raypos, raydir, tminmax, nodeaabb, primpos, primrot, primscale, template, raysat, rayaux, pl_count,
+    """The backward of _forward_impl: (grad_primpos, grad_primrot, grad_primscale, grad_template, grad_warp); the C entry
+    point is mvp_march_backward[_half][_depth]."""
+    (raypos, raydir, tminmax, nodeaabb, primpos, primrot, primscale, slabs, raysat, rayaux, pl_count,
      pl_list, warp, raydepth) = ctx.saved_tensors
+    half, depth = ctx.half, raydepth is not None
     if raysat is None:
-        raise RuntimeError("backward through mvpraymarch needs grad mode enabled during the forward call")
+        raise RuntimeError("backward through %s needs grad mode enabled during the forward call" %
+                           ("mvpraymarch_half" if half else "mvpraymarch"))
     fadescale, fadeexp = float(ctx.options["fadescale"]), float(ctx.options["fadeexp"])
     N, H, W = raypos.size(0), raypos.size(1), raypos.size(2)
     K = primpos.size(1)
-    TD, TH, TW = template.size(2), template.size(3), template.size(4)
+    TD, TH, TW = slabs.size(2), slabs.size(3), slabs.size(4)
     dev = raypos.device
     grad_rayrgba = aligned(grad_rayrgba.contiguous().float())
 
     # the library overwrites every element of the four gradients: no zero-fill pass (the reference needs
-    # torch.zeros_like x4 here, mvpraymarch.py:240-246)
+    # torch.zeros_like x4 here, mvpraymarch.py:240-246); the slab gradient is fp32 over fp16 slabs too
     grad_primpos = torch.empty_like(primpos)
     grad_primrot = torch.empty_like(primrot)
     grad_primscale = torch.empty_like(primscale)
-    grad_template = torch.empty_like(template)
+    grad_template = torch.empty(slabs.shape, device=dev, dtype=torch.float32)
     grad_warp = torch.empty_like(warp) if warp is not None else None
     WD, WH, WW = (warp.size(2), warp.size(3), warp.size(4)) if warp is not None else (0, 0, 0)
-    if raydepth is not None:  # (MVPRaymarchDepth)
+    if depth:
         grad_raydepth = (torch.zeros_like(raydepth) if grad_raydepth is None else grad_raydepth.contiguous().float())
-        with torch.cuda.device(dev), _hooks.timed("march_backward", dev):
-            _lib.check(_lib.get_lib().mvp_march_backward_depth(
-                N, H, W, K, ptr(raypos), ptr(raydir), ctx.stepsize, ptr(tminmax), ptr(nodeaabb), ptr(primpos),
-                ptr(primrot), ptr(primscale), TD, TH, TW, ptr(template), WD, WH, WW, ptr(warp), ptr(raysat),
-                ptr(rayaux), ptr(pl_count), ptr(pl_list), ctx.pl_cap, ptr(grad_rayrgba), ptr(grad_primpos),
-                ptr(grad_primrot), ptr(grad_primscale), ptr(grad_template), ptr(grad_warp), fadescale, fadeexp,
-                ptr(_hooks.diag), stream_ptr(dev), ptr(raydepth), ptr(grad_raydepth)), "mvp_march_backward_depth")
-        return grad_primpos, grad_primrot, grad_primscale, grad_template, grad_warp
-    with torch.cuda.device(dev), _hooks.timed("march_backward", dev):
-        _lib.check(_lib.get_lib().mvp_march_backward(
-            N, H, W, K, ptr(raypos), ptr(raydir), ctx.stepsize, ptr(tminmax), ptr(nodeaabb), ptr(primpos),
-            ptr(primrot), ptr(primscale), TD, TH, TW, ptr(template), WD, WH, WW, ptr(warp), ptr(raysat),
-            ptr(rayaux), ptr(pl_count), ptr(pl_list), ctx.pl_cap, ptr(grad_rayrgba), ptr(grad_primpos),
-            ptr(grad_primrot), ptr(grad_primscale), ptr(grad_template), ptr(grad_warp), fadescale, fadeexp,
-            ptr(_hooks.diag), stream_ptr(dev)), "mvp_march_backward")
+    name = "mvp_march_backward" + ("_half" if half else "") + ("_depth" if depth else "")
+    with torch.cuda.device(dev), _hooks.timed("march_backward_half" if half else "march_backward", dev):
+        args = ((N, H, W, K, ptr(raypos), ptr(raydir), ctx.stepsize, ptr(tminmax), ptr(nodeaabb), ptr(primpos),
+                 ptr(primrot), ptr(primscale), TD, TH, TW, ptr(slabs)) + (() if half else (WD, WH, WW, ptr(warp))) +
+                (ptr(raysat), ptr(rayaux), ptr(pl_count), ptr(pl_list), ctx.pl_cap, ptr(grad_rayrgba), ptr(grad_primpos),
+                 ptr(grad_primrot), ptr(grad_primscale), ptr(grad_template)) + (() if half else (ptr(grad_warp),)) +
+                (fadescale, fadeexp, ptr(_hooks.diag), stream_ptr(dev)) +
+                ((ptr(raydepth), ptr(grad_raydepth)) if depth else ()))
+        _lib.check(getattr(_lib.get_lib(), name)(*args), name)
     return grad_primpos, grad_primrot, grad_primscale, grad_template, grad_warp
 
 
@@ -370,9 +385,48 @@ class MVPRaymarchDepth(Function):
         return (None, None, None, None, gp, gr, gs, gt, None, None, None)
 
 
+class _MVPRaymarchHalf(Function):
+    """MVPRaymarch over fp16 slabs (halfslab.mvpraymarch_half): the march reads template_half, the slab gradient is the fp32
+    master `template`'s (straight-through rounding)."""
+
+    @staticmethod
+    def forward(ctx, raypos, raydir, stepsize, tminmax, primpos, primrot, primscale, template, template_half, gradmode,
+                options):
+        return _forward_impl(ctx, (raypos, raydir, tminmax), None, stepsize, primpos, primrot, primscale, template,
+                             None, gradmode, options, half=True, template_half=template_half)
+
+    @staticmethod
+    def backward(ctx, grad_rayrgba):
+        gp, gr, gs, gt, _ = _backward_impl(ctx, grad_rayrgba)
+        return (None, None, None, None, gp, gr, gs, gt, None, None, None)
+
+
+class _MVPRaymarchHalfFromCameras(Function):
+    """MVPRaymarchFromCameras over fp16 slabs (halfslab.mvpraymarch_half_from_cameras)."""
+
+    @staticmethod
+    def forward(ctx, campos, camrot, focal, princpt, pixelcoords, volradius, stepsize, primpos, primrot, primscale,
+                template, template_half, gradmode, options):
+        return _forward_impl(ctx, None, (campos, camrot, focal, princpt, pixelcoords, volradius), stepsize, primpos,
+                             primrot, primscale, template, None, gradmode, options, half=True, template_half=template_half)
+
+    @staticmethod
+    def backward(ctx, grad_rayrgba):
+        gp, gr, gs, gt, _ = _backward_impl(ctx, grad_rayrgba)
+        return (None, None, None, None, None, None, None, gp, gr, gs, gt, None, None, None)
+
+
 _DEFAULT_OPTIONS = {"algo": 0, "usebvh": "fixedorder", "sortprims": False, "randomorder": False, "maxhitboxes": 512,
                     "synchitboxes": True, "chlast": True, "fadescale": 8.0, "fadeexp": 8.0, "accum": 0,
                     "termthresh": 0.0, "griddim": 3, "blocksize": (8, 16), "bwdblocksize": (8, 16)}
+
+
+def _options(args):
+    """The option dict of the autograd Functions from mvpraymarch's keyword arguments (`args`: the caller's locals()); the
+    template reaches the Functions channels-last."""
+    opts = {k: args[k] for k in _DEFAULT_OPTIONS}
+    opts["chlast"] = True
+    return opts
 
 
 def mvpraymarch_from_cameras(campos, camrot, focal, princpt, pixelcoords, volradius, stepsize, primtransf, template,
@@ -388,11 +442,7 @@ def mvpraymarch_from_cameras(campos, camrot, focal, princpt, pixelcoords, volrad
     if not opts["chlast"]:
         template = template.permute(0, 1, 3, 4, 5, 2).contiguous()
         opts["chlast"] = True
-    if isinstance(primtransf, tuple):
-        primpos, primrot, primscale = primtransf
-    else:
-        primpos, primrot, primscale = (primtransf[:, :, 0, :].contiguous(), primtransf[:, :, 1:4, :].contiguous(),
-                                       primtransf[:, :, 4, :].contiguous())
+    primpos, primrot, primscale = _unpack_primtransf(primtransf)
     return MVPRaymarchFromCameras.apply(campos, camrot, focal, princpt, pixelcoords, volradius, stepsize, primpos,
                                         primrot, primscale, template, torch.is_grad_enabled(), opts)
 
@@ -427,51 +477,16 @@ def mvpraymarch(
     raypos, raydir: [N,H,W,3]; tminmax: [N,H,W,2]; primtransf: (primpos [N,K,3], primrot [N,K,3,3],
     primscale [N,K,3]) or packed [N,K,5,3]; template: [N,K,TD,TH,TW,4] (chlast=True) or [N,K,4,TD,TH,TW];
     returns rayrgba [N,H,W,4]."""
-    if isinstance(primtransf, tuple):
-        primpos, primrot, primscale = primtransf
-    else:  # packed layout, mvpraymarch.py:355-360
-        primpos, primrot, primscale = (
-            primtransf[:, :, 0, :].contiguous(),
-            primtransf[:, :, 1:4, :].contiguous(),
-            primtransf[:, :, 4, :].contiguous(),
-        )
+    opts = _options(locals())
+    primpos, primrot, primscale = _unpack_primtransf(primtransf)
     if not chlast:
         # the reference's kernels only ever read channels-last slabs; do the layout change here, where autograd
         # carries the gradient back to the caller's layout
         template = template.permute(0, 1, 3, 4, 5, 2).contiguous()
         if warp is not None:
             warp = warp.permute(0, 1, 3, 4, 5, 2).contiguous()
-
-    out = MVPRaymarch.apply(
-        raypos,
-        raydir,
-        stepsize,
-        tminmax,
-        primpos,
-        primrot,
-        primscale,
-        template,
-        warp,
-        rayterm,
-        torch.is_grad_enabled(),
-        {
-            "algo": algo,
-            "usebvh": usebvh,
-            "sortprims": sortprims,
-            "randomorder": randomorder,
-            "maxhitboxes": maxhitboxes,
-            "synchitboxes": synchitboxes,
-            "chlast": True,
-            "fadescale": fadescale,
-            "fadeexp": fadeexp,
-            "accum": accum,
-            "termthresh": termthresh,
-            "griddim": griddim,
-            "blocksize": blocksize,
-            "bwdblocksize": bwdblocksize,
-        },
-    )
-    return out
+    return MVPRaymarch.apply(raypos, raydir, stepsize, tminmax, primpos, primrot, primscale, template, warp, rayterm,
+                             torch.is_grad_enabled(), opts)
 
 
 def mvpraymarch_depth(
@@ -503,26 +518,17 @@ def mvpraymarch_depth(
     t_i: its lattice t), premultiplied by alpha like the colour and 0 where the ray hits nothing; the surface position image is
     raypos * alpha + raydir * raydepth (Raymarcher.forward(with_pos_img=True)).  Same arguments and options as mvpraymarch.
     Refused before any device work (NotImplementedError): algo=1 (the warp-field sampler) and fp16 slabs (mvpraymarch_half)."""
+    opts = _options(locals())
     if algo != 0:
         raise NotImplementedError("mvpraymarch_depth: only algo=0 (the slab sampler); the warp-field sampler has no depth "
                                   "channel")
     if torch.is_tensor(template) and template.dtype == torch.float16:
         raise NotImplementedError("mvpraymarch_depth: fp32 slabs only (the fp16 path, mvpraymarch_half, has no depth channel)")
-    if isinstance(primtransf, tuple):
-        primpos, primrot, primscale = primtransf
-    else:  # packed layout, mvpraymarch.py:355-360
-        primpos, primrot, primscale = (
-            primtransf[:, :, 0, :].contiguous(),
-            primtransf[:, :, 1:4, :].contiguous(),
-            primtransf[:, :, 4, :].contiguous(),
-        )
+    primpos, primrot, primscale = _unpack_primtransf(primtransf)
     if not chlast:
         template = template.permute(0, 1, 3, 4, 5, 2).contiguous()
-    return MVPRaymarchDepth.apply(
-        raypos, raydir, stepsize, tminmax, primpos, primrot, primscale, template, rayterm, torch.is_grad_enabled(),
-        {"algo": algo, "usebvh": usebvh, "sortprims": sortprims, "randomorder": randomorder, "maxhitboxes": maxhitboxes,
-         "synchitboxes": synchitboxes, "chlast": True, "fadescale": fadescale, "fadeexp": fadeexp, "accum": accum,
-         "termthresh": termthresh, "griddim": griddim, "blocksize": blocksize, "bwdblocksize": bwdblocksize})
+    return MVPRaymarchDepth.apply(raypos, raydir, stepsize, tminmax, primpos, primrot, primscale, template, rayterm,
+                                  torch.is_grad_enabled(), opts)
 
 
 def mvpraymarch_depth_from_cameras(*args, **kwargs):
